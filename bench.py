@@ -13,7 +13,14 @@ xGMI).  Rank 0 prints ONE JSON line.
 Timed region: the batch of step t is resident in HBM when step t starts - its host-to-device copy
 was issued on a copy stream during step t - 1, the way a pin_memory data loader feeds the reference - so every
 batch consumed after the first one is copied INSIDE the timed region, overlapped with compute.  The same loop fed
-from batches that never leave HBM is reported under also.resident_inputs.
+from batches that never leave HBM is reported under also.resident_inputs (--full).
+
+A plain run sets up, warms up, times --steps steps and prints the line (metric, value, unit, higher_is_better, dtype,
+ms_per_step, ...).  --full then measures everything else in the same process: the host's issue time on an idle
+device, the roofline steps of the instrumented kernel families, the extra legs under "also" (resident inputs, drop-in
+default, other mask ratio, fp32 parity mode, configs C / E / D, 16 frames) and the CPU baseline.  --dump-outputs DIR
+writes the loss, parameters and gradients of the last timed step as .npy files (inputs and initial weights are seeded:
+the same arguments give the same inputs in every run, so two builds can be compared output for output).
 
 Defaults: N = 1 -> BASELINE config B (8 frames per GPU, the reference yaml's BATCH_SIZE_PER_GPU); N > 1 -> BASELINE
 config C (global batch 32 on 8 GPUs = 4 frames per GPU, also used for its 2 / 4 GPU scaling points).
@@ -55,12 +62,19 @@ def parse():
     ap.add_argument("--mask-ratio", type=float, default=0.75)
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
     ap.add_argument("--pool", type=int, default=3, help="distinct pre-generated batches cycled through")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-also", action="store_true", help="skip the extra legs (resident inputs, fp32, mask 0.85, config E, config-C batch)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also measure everything else: host issue time on an idle device, the per-family roofline steps, "
+                         "the extra legs (resident inputs, drop-in default, other mask ratio, fp32, configs C / E / D, 16 frames) and the "
+                         "CPU baseline; off by default, where a run only sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (loss, flat parameters after the optimizer step, flat gradients) as "
+                         "DIR/<name>.npy, float32 / float64, < 64 MB in all")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the roofline steps")
+    ap.add_argument("--no-also", action="store_true", help="with --full: skip the extra legs (resident inputs, fp32, mask 0.85, config E, config-C batch)")
     ap.add_argument("--legs", choices=("default", "full"), default="default",
-                    help="kept for command-line compatibility: every leg, config D (fine-tune) included, is part of the default run since its "
-                         "dense convolutions are the library's own (round 5)")
+                    help="kept for command-line compatibility: --legs full is --full (every leg, config D (fine-tune) included, is part of "
+                         "the --full run since its dense convolutions are the library's own, round 5)")
     ap.add_argument("--feed", default="h2d", choices=["h2d", "resident"], help="h2d: every batch copied from pinned host memory inside the timed region")
     ap.add_argument("--prefetch", type=int, default=1, help="1: build the geometry plan of batch t+1 on a side stream")
     ap.add_argument("--plan-at", default="conv", choices=["start", "conv", "bwd"],
@@ -70,7 +84,9 @@ def parse():
                     help="0 (default): torch.autograd.set_multithreading_enabled(False) - the ~60 hand-written backward nodes of a step run on "
                          "the calling thread (0.8 ms less host time per step when issued into an idle device: 3.0 vs 3.8 ms, "
                          "tools/host_profile.py; no effect on the GPU-bound step); 1: torch's autograd worker thread (torch's default)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    args.full = args.full or args.legs == "full"
+    return args
 
 
 def algorithmic_bytes_per_frame(N, M, Ms, ds, G, a):
@@ -99,7 +115,11 @@ def measure_cpu_baseline(config: str, mask_ratio: float):
     # PyTorch-CPU slows down badly when oversubscribed on this workload (sparse gathers, many small ops): measured on the MI355X
     # host (256 logical CPUs) one step takes 5.1 s with 32 threads, 7.4 s with 64, 21 s with 128 and 643 s with 256 - a
     # convolution micro-probe picked 128 on some boxes, so the thread count is fixed at the best measured one
-    cores = min(32, avail)
+    try:                                              # a host share set through OMP_NUM_THREADS ("16", or a nested "16,8") is kept
+        share = int(os.environ.get("OMP_NUM_THREADS", "").split(",")[0].strip())
+    except ValueError:
+        share = 32
+    cores = max(1, min(32, avail, share))
     torch.set_num_threads(cores)
     cfg, ds, skw = configs.named_config(config, mask_ratio=mask_ratio)
     F = ds.point_feature_encoder.num_point_features
@@ -430,6 +450,25 @@ def _synth_boxes(rng, B, n_max, pcr, n_class):
     return out
 
 
+DUMP_MAX_ELEMS = 7_500_000      # per dumped array: loss + parameters + gradients stay under 64 MB
+
+
+def dump_outputs(path, wl):
+    """What the timed path hands its caller after its last step, as DIR/<name>.npy: `loss` (float64, shape (1,)), `params` and
+    `grads` (float32: the flat parameter buffer after the optimizer step and the flat gradient buffer of that step - every model
+    parameter and its .grad are views into them).  A buffer longer than DUMP_MAX_ELEMS is written as a fixed sample of its
+    entries: the same seeded, sorted indices for the same length, so that runs of two builds compare entry for entry."""
+    os.makedirs(path, exist_ok=True)
+    loss, _ = wl.last
+    arrays = {"loss": loss.detach().double().reshape(1), "params": wl.opt.flat_param, "grads": wl.opt.flat_grad}
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(0).choice(t.numel(), DUMP_MAX_ELEMS, replace=False))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy())
+
+
 def pin_rank_to_numa(local, world):
     """One rank per GPU on one host: bind the process to cores of the NUMA node its GPU hangs off (sysfs numa_node of the PCI
     function; the node's cpu list is split evenly between the ranks that land on it), so that eight ranks' interpreters,
@@ -521,7 +560,7 @@ def main():
     # N grows, which is what "scaling": "weak" in the line says and what the driver's efficiency (value(N) / (N value(1))) assumes.  Until
     # round 6 the default at N > 1 was config C's 4 frames per GPU (global batch 32 at N = 8): against the 8-frame N = 1 point that curve
     # could not exceed 0.78 even with a free gradient exchange (the 4-frame step is 4.6 - 4.9 ms for half the frames of the 7.4 - 7.7 ms
-    # 8-frame step).  Config C's share per GPU: --batch-per-gpu 4 (timed on one GPU in every default run: also.config_C_batch_4_per_gpu).
+    # 8-frame step).  Config C's share per GPU: --batch-per-gpu 4 (timed on one GPU in every --full run: also.config_C_batch_4_per_gpu).
     explicit_batch = args.batch_per_gpu is not None
     if args.batch_per_gpu is None:
         args.batch_per_gpu = 8
@@ -556,10 +595,12 @@ def main():
     wl.host_s = 0.0
     wait0 = gplan.EVENT_WAIT_S
     wl.opt.sync.measure = distd
+    opt_t0 = wl.opt.t
     t0 = time.perf_counter()
     wl.feed(args.steps, args.warmup)
     sync_all()
     dt = time.perf_counter() - t0
+    steps_timed = wl.opt.t - opt_t0                  # optimizer steps taken between the two clocks
     n_dev_alloc = torch.cuda.memory_stats(dev).get("num_device_alloc", 0) - n_dev_alloc0      # hipMalloc calls inside the timed region
     if trace_allocs:
         snap = torch.cuda.memory._snapshot()
@@ -583,12 +624,17 @@ def main():
         host_ms, exposed_ms, host_wait_ms = float(hx[0].item()), float(hx[1].item()), -float(hx[2].item())
     frames = B * world * args.steps
     fps = frames / dt
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, wl)            # before anything below takes further steps
+    loss, bd = wl.last
+    final_loss = float(loss.detach())
+    assert np.isfinite(final_loss), "training diverged"
     wl.advance = False
     # what the host needs to ISSUE a step when nothing makes it wait (device idle at the start of every step, the wait for the plan's
     # event excluded): the split of host_ms_per_step / host_wait_ms_per_step above moves with where a full launch queue happens to block
     # the issuing thread, this number does not
     host_idle_ms = None
-    if wl.mae and args.prefetch:
+    if args.full and wl.mae and args.prefetch:
         wl.pre_sync = True
         wl.feed(2, args.warmup)                       # (first steps after the switch: pending plan handed over)
         h0, w0 = wl.host_s, gplan.EVENT_WAIT_S
@@ -600,9 +646,6 @@ def main():
             hi = torch.tensor([host_idle_ms], dtype=torch.float64, device=dev)
             dist.all_reduce(hi, op=dist.ReduceOp.MAX)
             host_idle_ms = float(hi.item())
-    loss, bd = wl.last
-    final_loss = float(loss.detach())
-    assert np.isfinite(final_loss), "training diverged"
 
     pre = args.config in ("A", "B", "E")
     out = {"metric": "MAE pre-train frames/sec (Waymo-shape, 180k pts, 75% mask)" if pre else "fine-tune frames/sec (KITTI-shape, CenterPoint head)",
@@ -625,6 +668,7 @@ def main():
                       "autograd": "backward nodes on the calling thread (torch.autograd.set_multithreading_enabled(False))" if not args.autograd_thread
                                   else "torch default (autograd worker thread)",
                       "params": n_params, "mask_ratio": args.mask_ratio if pre else None, "loss_last": round(final_loss, 5),
+                      "optimizer_steps_timed": steps_timed,
                       "inputs": ("pinned host batches; batch t+1 copied on a copy stream during step t (inside the timed region), "
                                  "batch 0 resident when the clock starts" if args.feed == "h2d" else "resident in HBM"),
                       "outputs_skipped": ["batch_dict['spatial_features'] dense (B,128,Y,X) map - the pre-training step consumes the "
@@ -643,7 +687,7 @@ def main():
     # of the step (as before round 5's last change), not under the decoder's tile convolution - a bracket around that launch would
     # otherwise time the plan's kernels with it (0.47 -> 0.37 of the matrix-core peak in the same run)
     plan_at, args.plan_at = args.plan_at, "start"
-    roofline = measure_roofline(wl.step, lambda n: wl.feed(n, total_steps - 1), 4) if (not args.no_roofline and wl.mae) else None
+    roofline = measure_roofline(wl.step, lambda n: wl.feed(n, total_steps - 1), 4) if (args.full and not args.no_roofline and wl.mae) else None
     args.plan_at = plan_at
     loss, bd = wl.last
     vox, ep = bd.get("_gdmae_vox"), bd.get("_gdmae_plan")
@@ -665,7 +709,7 @@ def main():
                 "frames_per_gpu": w.B, "leg_wall_s": round(time.perf_counter() - t_leg0, 1)}
 
     also = {}
-    if world == 1 and not args.no_also and pre:
+    if args.full and world == 1 and not args.no_also and pre:
         # ---- the same loop with batches that never leave HBM (what round 1 / 2 reported as the headline)
         other_feed = wl.feed_resident if args.feed == "h2d" else wl.feed_h2d
         also["resident_inputs" if args.feed == "h2d" else "h2d_inclusive"] = timed_leg(wl, 2, args.steps, other_feed)
@@ -698,7 +742,7 @@ def main():
             # ... and the headline's step at twice the reference's per-GPU batch: how much of the step is per-launch cost that more rows per
             # launch amortise (the fused layer launches' weight stream per 32-row tile, ~7 us of fixed cost per launch)
             extra.append(("config_B_batch_16_per_gpu", "B", 16))
-            # config D (fine-tune step) is part of the default run since round 5: its dense convolutions are the library's own
+            # config D (fine-tune step) is one of these legs since round 5: its dense convolutions are the library's own
             # (csrc/conv_dense.hip), there is no MIOpen search at first use any more
             extra.append(("config_D_finetune", "D", 8))
             for key, cfg_name, b in extra:
@@ -760,7 +804,7 @@ def main():
         if roofline is not None:
             out["roofline"] = roofline
         shares = os.path.join(REPO, "profiles", "class_shares.json")
-        if os.path.exists(shares):
+        if args.full and os.path.exists(shares):
             # NOT measured in this run: the committed one-step rocprofv3 trace of the builder's profiling box
             out["kernel_time_shares_profiling_box"] = json.load(open(shares))
         if also:
@@ -768,7 +812,7 @@ def main():
             if isinstance(also.get("drop_in_default"), dict) and "value" in also["drop_in_default"]:
                 # what a tools/train.py user gets without touching a switch (the reference module's dense spatial_features map written)
                 out["config"]["drop_in_default_frames_per_s"] = also["drop_in_default"]["value"]
-        if not args.no_cpu_baseline and world == 1 and pre:      # reported at N = 1 only (rank 0's host cores)
+        if args.full and not args.no_cpu_baseline and world == 1 and pre:      # reported at N = 1 only (rank 0's host cores)
             out["cpu_baseline"] = measure_cpu_baseline(args.config, args.mask_ratio)
         sys.stdout.flush()
         try:

@@ -5,7 +5,7 @@ set -u
 TAG=${1:-r01}
 OUT=$PWD/gpurun_out/profiles_$TAG
 mkdir -p $OUT
-python bench.py > $OUT/bench_full.log 2>&1
+python bench.py --full > $OUT/bench_full.log 2>&1
 tail -1 $OUT/bench_full.log > $OUT/${TAG}_bench_n1.json
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats -f csv -T -d /tmp/prof_kt -- python /root/repo/bench.py --steps 12 --warmup 6 --no-cpu-baseline --no-roofline --no-also > /tmp/kt.log 2>&1

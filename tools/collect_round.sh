@@ -5,7 +5,7 @@ set -u
 TAG=${1:-r02}
 OUT=$PWD/gpurun_out/profiles_$TAG
 mkdir -p $OUT
-if [ -z "${SKIP_BENCH:-}" ]; then python bench.py --legs full > $OUT/bench_full.log 2>&1; fi
+if [ -z "${SKIP_BENCH:-}" ]; then python bench.py --full > $OUT/bench_full.log 2>&1; fi
 if [ -z "${SKIP_BENCH:-}" ]; then tail -1 $OUT/bench_full.log > $OUT/${TAG}_bench_n1.json; fi
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/prof_kt

@@ -10,7 +10,7 @@ mkdir -p gpurun_out
 export GDMAE_BENCH_RESERVE_GB=1 GDMAE_BENCH_PIN=1
 pids=()
 for k in $(seq 0 $((N - 1))); do
-  GDMAE_BENCH_PIN_SLICE=$k/$N python bench.py --batch-per-gpu $FR --steps $STEPS --warmup 5 --no-cpu-baseline --no-also --no-roofline \
+  GDMAE_BENCH_PIN_SLICE=$k/$N python bench.py --batch-per-gpu $FR --steps $STEPS --warmup 5 --full --no-cpu-baseline --no-also --no-roofline \
     > gpurun_out/proc${N}_$k.json 2> gpurun_out/proc${N}_$k.err &
   pids+=($!)
 done

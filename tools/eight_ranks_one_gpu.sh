@@ -7,7 +7,7 @@
 N=${1:-8}; STEPS=${2:-8}
 cd "$(dirname "$0")/.."
 export GDMAE_DIST_BACKEND=gloo GDMAE_BENCH_RESERVE_GB=1 HSA_ENABLE_IPC_MODE_LEGACY=0
-python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus $N \
+python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus $N --full \
   --steps $STEPS --warmup 3 --no-cpu-baseline --no-also --no-roofline 2>gpurun_out/ranks$N.err | tail -1 > gpurun_out/ranks$N.json
 python - <<PY
 import json

@@ -1,4 +1,4 @@
-"""One line per bench log: frames/s, ms per step, time of the token-GEMM family and of the kernels named on the command line."""
+"""One line per bench.py --full log: frames/s, ms per step, time of the token-GEMM family and of the kernels named on the command line."""
 import sys, json
 for l in open(sys.argv[1]):
     if l.startswith('{"metric"'):

@@ -1,3 +1,4 @@
+"""Frames/s, ms per step and the tile convolution's roofline figures of a bench.py --full line (the last line on stdin)."""
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 r=d["roofline"]; a=dict(r["also"]); a[r["kernel"]]=r
