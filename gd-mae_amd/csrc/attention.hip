@@ -545,19 +545,6 @@ int gd_attn_mfma_bwd(const void* qk, const void* v, const void* dout, void* dqk,
                      const int* csr_tok, const int* win_start, const int* win_len, int n_win, int T, int d, int H,
                      const float* tau, float tau_min, hipStream_t st);
 
-// bf16-MFMA variant of the T = 32 / 64 levels for bf16 token I/O (attention_t32.hip)
-int gd_attn_t32_fwd(const void* qk, const void* v, void* out, const int* csr_tok, const int* win_start, const int* win_len, int n_win,
-                    int T, int d, int H, const float* tau, float tau_min, hipStream_t st);
-int gd_attn_t32_bwd(const void* qk, const void* v, const void* dout, void* dqk, void* dv, float* dtau_part, const int* csr_tok,
-                    const int* win_start, const int* win_len, int n_win, int T, int d, int H, const float* tau, float tau_min,
-                    hipStream_t st);
-
-int gd_attn_t3264_fwd(const void* qk, const void* v, void* out, const int* csr_tok, const int* ws32, const int* wl32, int n32, const int* ws64,
-                      const int* wl64, int n64, int d, int H, const float* tau, float tau_min, hipStream_t st);
-int gd_attn_t3264_bwd(const void* qk, const void* v, const void* dout, void* dqk, void* dv, const int* csr_tok, const int* ws32,
-                      const int* wl32, int n32, float* part32, const int* ws64, const int* wl64, int n64, float* part64, int d, int H,
-                      const float* tau, float tau_min, hipStream_t st);
-
 // workgroup-cooperative kernels, all levels of a layer in one launch per direction (attention_coop.hip, round 5): whole row segments
 // through LDS, 16 bytes per lane; the forward leaves the rows' log-sum-exp for the backward, which also reads the forward's output
 int gd_attn_levels_fwd(const void* qk, const void* v, void* out, float* lse, const int* csr_tok, const int* ws16, const int* wl16, int n16,
@@ -573,15 +560,13 @@ int gd_attn_t16_fwd(const void* qk, const void* v, void* out, const int* csr_tok
 int gd_attn_t16_bwd(const void* qk, const void* v, const void* dout, void* dqk, void* dv, float* dtau_part, const int* csr_tok,
                     const int* win_start, const int* win_len, int n_win, int d, int H, const float* tau, float tau_min, hipStream_t st);
 
-// 0: bf16 I/O on the bf16 matrix-core kernels at every level (attention_t16.hip, attention_t32.hip), fp32 I/O
-//    on the exact-fp32 MFMA kernels for T >= 32 and the lane-per-query VALU kernels for T = 16;
-// 1: VALU kernels only;  2: like 0 but always the exact-fp32 MFMA kernels for T >= 32 and the VALU kernels for T = 16;
-// 3: like 0 with the round-4 one-wavefront-per-(window, head) kernels for the bf16 T = 32 / 64 levels (attention_t32.hip) instead of the
-//    workgroup-cooperative ones (attention_coop.hip) - A/B reference
+// 0: bf16 I/O on the bf16 matrix-core kernels (attention_coop.hip, and attention_t16.hip for T = 16 on its own), except the T = 32 / 64
+//    levels of a backward without the forward's log-sum-exp rows; everything else on the exact-fp32 MFMA kernels for T >= 32 and the
+//    lane-per-query VALU kernels for T = 16;
+// 1: VALU kernels only;  2: always the exact-fp32 MFMA kernels for T >= 32 and the VALU kernels for T = 16
 static int g_attn_impl = 0;
-static inline bool attn_auto() { return g_attn_impl == 0 || g_attn_impl == 3; }
 extern "C" int gdmae_set_attention_impl(int impl) {
-  GD_REQUIRE(impl >= 0 && impl <= 3, "attention impl: 0 (auto), 1 (VALU only), 2 (fp32 MFMA) or 3 (auto, per-(window, head) bf16 kernels)");
+  GD_REQUIRE(impl >= 0 && impl <= 2, "attention impl: 0 (auto), 1 (VALU only) or 2 (fp32 MFMA)");
   g_attn_impl = impl;
   return 0;
 }
@@ -598,15 +583,13 @@ extern "C" int gdmae_window_attention_fwd(const void* qk, const void* v, void* o
   GD_REQUIRE(T == 16 || T == 32 || T == 64, "T must be 16/32/64");
   GD_REQUIRE(H % (GD_WAVE / T) == 0, "heads must pack evenly into a wavefront");
   hipStream_t st = (hipStream_t)stream;
-  if (attn_auto() && T == 16 && io_bf16 && H % 4 == 0)
+  if (g_attn_impl == 0 && T == 16 && io_bf16 && H % 4 == 0)
     return gd_attn_t16_fwd(qk, v, out, csr_tok, win_start, win_len, n_win, d, H, tau, tau_min, st);
   if (g_attn_impl == 0 && T >= 32 && io_bf16 && H % 4 == 0)
     return T == 32 ? gd_attn_levels_fwd(qk, v, out, nullptr, csr_tok, nullptr, nullptr, 0, win_start, win_len, n_win, nullptr, nullptr, 0, d, H, tau,
                                         tau_min, st)
                    : gd_attn_levels_fwd(qk, v, out, nullptr, csr_tok, nullptr, nullptr, 0, nullptr, nullptr, 0, win_start, win_len, n_win, d, H, tau,
                                         tau_min, st);
-  if (attn_auto() && T >= 32 && io_bf16)
-    return gd_attn_t32_fwd(qk, v, out, csr_tok, win_start, win_len, n_win, T, d, H, tau, tau_min, st);
   if (g_attn_impl != 1 && T >= 32)
     return gd_attn_mfma_fwd(qk, v, out, io_bf16, csr_tok, win_start, win_len, n_win, T, d, H, tau, tau_min, st);
   AttnArgs A{qk, v, out, csr_tok, win_start, win_len, n_win, d, H, tau, tau_min};
@@ -624,10 +607,8 @@ extern "C" int gdmae_window_attention_bwd(const void* qk, const void* v, const v
   GD_REQUIRE(T == 16 || T == 32 || T == 64, "T must be 16/32/64");
   GD_REQUIRE(H % (GD_WAVE / T) == 0, "heads must pack evenly into a wavefront");
   hipStream_t st = (hipStream_t)stream;
-  if (attn_auto() && T == 16 && io_bf16 && H % 4 == 0)
+  if (g_attn_impl == 0 && T == 16 && io_bf16 && H % 4 == 0)
     return gd_attn_t16_bwd(qk, v, dout, dqk, dv, dtau_part, csr_tok, win_start, win_len, n_win, d, H, tau, tau_min, st);
-  if (attn_auto() && T >= 32 && io_bf16)
-    return gd_attn_t32_bwd(qk, v, dout, dqk, dv, dtau_part, csr_tok, win_start, win_len, n_win, T, d, H, tau, tau_min, st);
   if (g_attn_impl != 1 && T >= 32)
     return gd_attn_mfma_bwd(qk, v, dout, dqk, dv, io_bf16, dtau_part, csr_tok, win_start, win_len, n_win, T, d, H, tau,
                             tau_min, st);
@@ -637,8 +618,8 @@ extern "C" int gdmae_window_attention_bwd(const void* qk, const void* v, const v
 
 
 // All occupancy levels of one shift (the windows of level l are win_start / win_len [sum_{k<l} n_win[k], ...)), as the layer
-// executor issues them: bf16 rows on the matrix-core kernels go out as two launches (T = 16; T = 32 and T = 64 together),
-// everything else level by level.  Backward: dtau_part holds sum_l n_win[l] * H partial slots, level after level.
+// executor issues them: bf16 rows go out as one launch per direction (attention_coop.hip; the backward only when it gets the forward's
+// log-sum-exp rows), everything else level by level.  Backward: dtau_part holds sum_l n_win[l] * H partial slots, level after level.
 // Both entries are measurement slots (common.h GdTimed: HIP-event brackets on the launch stream, bench.py's roofline leg).
 long long g_attn_tokens = 0;   // tokens of the layer whose attention entry is called next (set by the layer executor)
 void gd_attn_timing_tokens(long long n) { g_attn_tokens = n; }
@@ -649,7 +630,7 @@ static double attn_alg_bytes(int n_levels, const int* n_win, const int* win_len_
 }
 
 static bool levels_fast_path(int io_bf16, int n_levels, const int* max_tokens, int H, int d) {
-  if (!attn_auto() || !io_bf16 || H % 4 != 0 || d % H != 0 || (d / H != 16 && d / H != 32)) return false;
+  if (g_attn_impl != 0 || !io_bf16 || H % 4 != 0 || d % H != 0 || (d / H != 16 && d / H != 32)) return false;
   for (int l = 0; l < n_levels; ++l)
     if (max_tokens[l] != 16 && max_tokens[l] != 32 && max_tokens[l] != 64) return false;
   return true;
@@ -657,7 +638,7 @@ static bool levels_fast_path(int io_bf16, int n_levels, const int* max_tokens, i
 // 1 when gdmae_window_attention_levels_fwd with these arguments (and the current gdmae_set_attention_impl) writes `lse` - the caller hands
 // `out` / `lse` to the backward only then (a backward after an implementation switch must not read rows the forward never wrote)
 extern "C" int gdmae_window_attention_levels_writes_lse(int io_bf16, int n_levels, const int* max_tokens, int d, int H) {
-  return (levels_fast_path(io_bf16, n_levels, max_tokens, H, d) && g_attn_impl == 0) ? 1 : 0;
+  return levels_fast_path(io_bf16, n_levels, max_tokens, H, d) ? 1 : 0;
 }
 extern "C" int gdmae_window_attention_levels_fwd(const void* qk, const void* v, void* out, int io_bf16, const int* csr_tok,
                                                  const int* win_start, const int* win_len, int n_levels, const int* n_win,
@@ -667,10 +648,10 @@ extern "C" int gdmae_window_attention_levels_fwd(const void* qk, const void* v, 
   // algorithmic bytes: q, k, v rows read + out row written per token (4 d elements) + CSR; the token count is not an argument
   // of this entry - the caller (encoder_layer.hip) adds it through gd_attn_timing_tokens
   // side bytes (what the launch moves besides by design): the (n_tok, H) fp32 log-sum-exp rows the cooperative path leaves for the backward
-  const bool lse_path = levels_fast_path(io_bf16, n_levels, max_tokens, H, d) && g_attn_impl == 0;
+  const bool fast = levels_fast_path(io_bf16, n_levels, max_tokens, H, d);
   GdTimed timed(GD_T_ATTN_FWD, st, attn_alg_bytes(n_levels, n_win, nullptr, g_attn_tokens, d, io_bf16 ? 2 : 4, 4), 0.0,
-                (lse_path && lse) ? 4.0 * H * (double)g_attn_tokens : 0.0);
-  if (!levels_fast_path(io_bf16, n_levels, max_tokens, H, d)) {
+                (fast && lse) ? 4.0 * H * (double)g_attn_tokens : 0.0);
+  if (!fast) {
     int base = 0;
     for (int l = 0; l < n_levels; ++l) {
       const int rc = gdmae_window_attention_fwd(qk, v, out, io_bf16, csr_tok, win_start + base, win_len + base, n_win[l], max_tokens[l], d, H,
@@ -689,13 +670,7 @@ extern "C" int gdmae_window_attention_levels_fwd(const void* qk, const void* v, 
     ws[k] = win_start + base; wl[k] = win_len + base; nw[k] = n_win[l];
     base += n_win[l];
   }
-  if (g_attn_impl == 0)
-    return gd_attn_levels_fwd(qk, v, out, lse, csr_tok, ws[0], wl[0], nw[0], ws[1], wl[1], nw[1], ws[2], wl[2], nw[2], d, H, tau, tau_min, st);
-  if (nw[0] > 0) {
-    const int rc = gd_attn_t16_fwd(qk, v, out, csr_tok, ws[0], wl[0], nw[0], d, H, tau, tau_min, st);
-    if (rc != 0) return rc;
-  }
-  return gd_attn_t3264_fwd(qk, v, out, csr_tok, ws[1], wl[1], nw[1], ws[2], wl[2], nw[2], d, H, tau, tau_min, st);
+  return gd_attn_levels_fwd(qk, v, out, lse, csr_tok, ws[0], wl[0], nw[0], ws[1], wl[1], nw[1], ws[2], wl[2], nw[2], d, H, tau, tau_min, st);
 }
 
 extern "C" int gdmae_window_attention_levels_bwd(const void* qk, const void* v, const void* dout, void* dqk, void* dv, int io_bf16,
@@ -706,16 +681,17 @@ extern "C" int gdmae_window_attention_levels_bwd(const void* qk, const void* v, 
   // algorithmic bytes = the minimum of an attention backward (q, k, v, dOut rows in, dq, dk, dv rows out: 7 rows per token); side bytes =
   // what this design reads on top of it INSTEAD of re-deriving the softmax statistics - the forward's output rows O (D = dO . O) and the
   // log-sum-exp rows - and the per-(window, head) dtau partial slots it writes
+  // (a backward without them takes the per-level loop: no configuration gets there, every one has nhead = 8)
+  const bool fast = levels_fast_path(io_bf16, n_levels, max_tokens, H, d) && out != nullptr && lse != nullptr;
   double side = 0.0;
   {
     long long nwin = 0;
     for (int l = 0; l < n_levels; ++l) nwin += n_win[l];
     side = 4.0 * H * (double)nwin;
-    if (levels_fast_path(io_bf16, n_levels, max_tokens, H, d) && g_attn_impl == 0 && out != nullptr && lse != nullptr)
-      side += (double)g_attn_tokens * ((double)d * (io_bf16 ? 2 : 4) + 4.0 * H);
+    if (fast) side += (double)g_attn_tokens * ((double)d * (io_bf16 ? 2 : 4) + 4.0 * H);
   }
   GdTimed timed(GD_T_ATTN_BWD, st, attn_alg_bytes(n_levels, n_win, nullptr, g_attn_tokens, d, io_bf16 ? 2 : 4, 7), 0.0, side);
-  if (!levels_fast_path(io_bf16, n_levels, max_tokens, H, d)) {
+  if (!fast) {
     int base = 0;
     long long pbase = 0;
     for (int l = 0; l < n_levels; ++l) {
@@ -739,12 +715,6 @@ extern "C" int gdmae_window_attention_levels_bwd(const void* qk, const void* v, 
     base += n_win[l];
     pbase += (long long)n_win[l] * H;
   }
-  if (g_attn_impl == 0 && out != nullptr && lse != nullptr)
-    return gd_attn_levels_bwd(qk, v, out, lse, dout, dqk, dv, csr_tok, ws[0], wl[0], nw[0], part[0], ws[1], wl[1], nw[1], part[1], ws[2], wl[2], nw[2],
-                              part[2], d, H, tau, tau_min, st);
-  if (nw[0] > 0) {
-    const int rc = gd_attn_t16_bwd(qk, v, dout, dqk, dv, part[0], csr_tok, ws[0], wl[0], nw[0], d, H, tau, tau_min, st);
-    if (rc != 0) return rc;
-  }
-  return gd_attn_t3264_bwd(qk, v, dout, dqk, dv, csr_tok, ws[1], wl[1], nw[1], part[1], ws[2], wl[2], nw[2], part[2], d, H, tau, tau_min, st);
+  return gd_attn_levels_bwd(qk, v, out, lse, dout, dqk, dv, csr_tok, ws[0], wl[0], nw[0], part[0], ws[1], wl[1], nw[1], part[1], ws[2], wl[2], nw[2],
+                            part[2], d, H, tau, tau_min, st);
 }

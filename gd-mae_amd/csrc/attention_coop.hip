@@ -1,7 +1,7 @@
 // Workgroup-cooperative bf16-MFMA windowed cosine attention, T = 32 / 64 occupancy levels (throughput mode; round 5).
 //
 // Contract and arithmetic: reference cosine_msa.py:114-176 / sst_basic_block.py:22-54 through the window CSR, exactly as
-// attention_t32.hip (raw-operand logits normalised on the accumulator, S^T layout for the forward and dQ, S layout for dK / dV, no
+// the round-4 per-(window, head) kernels (raw-operand logits normalised on the accumulator, S^T layout for the forward and dQ, S layout for dK / dV, no
 // atomics).  What is new is how rows travel (attn_tiles.h): a workgroup = one window x HW heads whose row segments are contiguous
 // (T = 64: 2 heads x 2 wavefronts, T = 32: 4 heads x 1 wavefront); all 256 threads load the q / k / v (/ dO) segments of the window's rows
 // 16 bytes per lane - whole cache lines - into the swizzled LDS tiles, the wavefronts take their MFMA operand pieces from there, and the

@@ -15,7 +15,7 @@
 //    the same factors are folded into dS before it is rounded to bf16 for the dQ / dK products, whose A operands are again
 //    the raw rows (read transposed from LDS with ds_read_b64_tr_b16);
 //  * softmax statistics: 4 accumulator registers per lane + a cross-group reduction with v_permlane16/32_swap;
-//  * the backward evaluates the scores in both orientations, like attention_t32.hip (S^T with the query on the lane for dQ, S with the
+//  * the backward evaluates the scores in both orientations, like the T = 32 / 64 cooperative kernels (S^T with the query on the lane for dQ, S with the
 //    key on the lane for dK / dV), so there are no atomics and gradients are deterministic.
 #pragma once
 #include "common.h"

@@ -1,5 +1,5 @@
 // Shared pieces of the workgroup-cooperative bf16 attention kernels (attention_coop.hip): operand rows, swizzled row-major LDS tiles,
-// MFMA wrappers (the operand scheme of attention_t32.hip) and the COOPERATIVE row transfer - a workgroup moves the rows of a window as
+// MFMA wrappers (the operand scheme of the round-4 per-(window, head) kernels) and the COOPERATIVE row transfer - a workgroup moves the rows of a window as
 // whole 64 ... 256-byte segments, 16 bytes per lane, through the LDS tiles the products read anyway.
 //
 // Why: the per-(window, head) kernels load a token row as DH / 8 8-byte pieces per lane (the MFMA operand layout), i.e. every load
@@ -54,7 +54,7 @@ __device__ __forceinline__ float grp_max(float x) {
   return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
 }
 
-// Tiles are row-major [token][32 bf16]; the eight 8-byte units of a row are XOR-permuted by a function of the row (as attention_t32.hip:
+// Tiles are row-major [token][32 bf16]; the eight 8-byte units of a row are XOR-permuted by a function of the row (as in the round-4 kernels:
 // conflict-free ds_write_b64 / ds_read_b64 of the operand pieces, transposed reads touch whole rows).  swz() is that function.
 __device__ __forceinline__ int swz(int row) { return (((row >> 1) ^ (row >> 4)) & 1) | (((row >> 2) & 3) << 1); }
 __device__ __forceinline__ int unit_off(int row, int unit) { return row * kPitch + 4 * (unit ^ swz(row)); }

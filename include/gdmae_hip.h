@@ -325,12 +325,12 @@ int gdmae_segmax_bn_bwd(const void* x, int x_bf16, const float* out, const int* 
  * qk (Ms, 2d): projected queries [0,d) and keys [d,2d); v (Ms, d); out (Ms, d) written at token rows;
  * io_bf16 selects fp32 (0) or bf16 (1) rows in HBM - arithmetic is fp32 in registers either way.
  * Backward: dqk (Ms,2d), dv (Ms,d), dtau_part: n_win*H floats (partials of d loss / d clamp(tau)).
- * bf16 rows run on the bf16 matrix cores at every level: v_mfma_f32_16x16x{16,32}_bf16 with one wavefront per
- * window x 4 heads at T = 16 (attention_t16.hip), v_mfma_f32_32x32x16_bf16 at T = 32 (one wavefront per window x head)
- * and T = 64 (two wavefronts per window x head) (attention_t32.hip); logits come from the raw bf16 rows (exact products,
- * fp32 accumulation) and are normalised afterwards.  fp32 rows: exact fp32 v_mfma_f32_32x32x2_f32 for T >= 32
- * (attention_mfma.hip), lane-per-query VALU kernel for T = 16.  gdmae_set_attention_impl: 0 = that default, 1 = VALU
- * kernels everywhere, 2 = fp32 MFMA (T >= 32) / VALU (T = 16) also for bf16 rows (A/B tests). */
+ * bf16 rows (H % 4 == 0) run on the bf16 matrix cores: v_mfma_f32_16x16x{16,32}_bf16 with one wavefront per window x 4 heads
+ * at T = 16 (attention_t16.hip), the workgroup-cooperative forward at T = 32 / 64 (attention_coop.hip); logits come from the raw
+ * bf16 rows (exact products, fp32 accumulation) and are normalised afterwards.  Everything else, the bf16 T = 32 / 64 backward
+ * of this entry included: exact fp32 v_mfma_f32_32x32x2_f32 for T >= 32 (attention_mfma.hip), lane-per-query VALU kernel for
+ * T = 16.  gdmae_set_attention_impl: 0 = that default, 1 = VALU kernels everywhere, 2 = fp32 MFMA (T >= 32) / VALU (T = 16)
+ * also for bf16 rows (A/B tests); any other value is an error. */
 int gdmae_set_attention_impl(int impl);
 int gdmae_window_attention_fwd(const void* qk, const void* v, void* out, int io_bf16, const int* csr_tok,
                                const int* win_start, const int* win_len, int n_win, int T, int d, int H,
@@ -343,8 +343,8 @@ int gdmae_window_attention_bwd(const void* qk, const void* v, const void* dout, 
  * sum_l n_win[l] * H partial slots, level after level.  bf16 rows with levels of 16 / 32 / 64 tokens go out as ONE launch per direction
  * (csrc/attention_coop.hip), everything else level by level through the functions above.
  * lse (forward, optional): (n_tok, H) fp32, receives log2 sum_k exp(logit) of every row of the T = 32 / 64 levels; the backward takes it
- * back together with the forward's output rows `out` (both optional there: without them the backward re-derives the softmax statistics on
- * the one-wavefront-per-(window, head) kernels). */
+ * back together with the forward's output rows `out` (both optional there: without them the backward goes level by level through the
+ * functions above; no configuration gets there, every one has nhead = 8). */
 /* 1 when the forward below, called with these arguments under the current gdmae_set_attention_impl, writes `lse`: only then may `out` /
  * `lse` be handed to the backward (max_tokens: HOST array of n_levels ints) */
 int gdmae_window_attention_levels_writes_lse(int io_bf16, int n_levels, const int* max_tokens, int d, int H);
@@ -560,13 +560,11 @@ typedef struct gdmae_layer_args {
 /* Packed weight image of one layer (bf16 mode): forward operands [Win(q,k rows) | Win(v rows) | Wo | W1 | W2] followed by
  * the transposed operands of the input-gradient products [W2^T | W1^T | Wo^T | Win(q,k)^T | Win(v)^T].
  * gdmae_layer_pack_jobs fills a HOST table of gdmae_layer_pack_job_count(d, ff) x 6 int64 {src, dst, M, K, ld, flags} for gdmae_tok_gemm_pack
- * (copy it to the device; one launch packs any number of layers). */
+ * (copy it to the device; one launch packs any number of layers): the ten images above. */
 size_t gdmae_layer_packed_bytes(int d, int ff);
 int gdmae_layer_pack_jobs(const float* Win, const float* Wo, const float* W1, const float* W2, int d, int ff, void* packed,
                           long long* jobs_host /* 6 x gdmae_layer_pack_job_count(d, ff) */);
-/* Jobs gdmae_layer_pack_jobs writes: the ten images above plus, for d in {128, 256} and ff = 2 d, the weight STREAM of the
- * in-register forward launch (csrc/layer_v3.hip: Wo, then per 128-channel hidden chunk W1[chunk rows] and W2[:, chunk columns] as
- * 16 x 32 matrix-core fragments in the order the launch consumes them; EncoderLayer's linears, sst_basic_block.py:57-84). */
+/* Jobs gdmae_layer_pack_jobs writes (10). */
 int gdmae_layer_pack_job_count(int d, int ff);
 int gdmae_tok_gemm_pack(const long long* jobs_dev, int n_jobs, void* stream);
 /* Y = epilogue(X Wp^T + bias): X (n_pad, K) bf16 rows (n_pad % 64 == 0), Wp = packed (N, K) weights, bias (N) bf16 or

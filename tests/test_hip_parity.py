@@ -209,9 +209,9 @@ def test_sparse_conv_matches_oracle():
 @pytest.mark.parametrize("impl", [0, 1, 2])
 @pytest.mark.parametrize("d,nhead", [(128, 8), (256, 8)])
 def test_window_attention_fwd_bwd_matches_oracle(d, nhead, impl):
-    """impl 0 (product default): bf16 rows on the bf16 matrix-core kernels at every level (attention_t16 / attention_t32),
-    fp32 rows on the exact-fp32 MFMA kernels for T = 32 / 64 and the VALU kernel for T = 16; 1: VALU everywhere; 2: exact-fp32
-    MFMA (T >= 32) / VALU (T = 16) also for bf16 rows.  The bf16-row results of the three implementations must agree with
+    """impl 0 (product default): bf16 rows on the bf16 matrix-core kernels (attention_coop, and attention_t16 for a T = 16 level
+    on its own), fp32 rows on the exact-fp32 MFMA kernels for T = 32 / 64 and the VALU kernel for T = 16; 1: VALU everywhere;
+    2: exact-fp32 MFMA (T >= 32) / VALU (T = 16) also for bf16 rows.  The bf16-row results of the three implementations must agree with
     each other far below bf16 noise."""
     from gdmae_hip import lib as L
     from gdmae_hip import ops, plan
@@ -328,7 +328,7 @@ def test_packed_window_attention_edge_cases(d, H):
         part = torch.full((sum(n_win) * H,), 123.0, device=dv)             # every slot must be written
         if levels_entry:
             # "lse": the product path - the forward leaves the rows' log-sum-exp, the backward takes it and the forward's output
-            # (one launch per direction); True: without them (the backward re-derives the statistics, per-(window, head) kernels)
+            # (one launch per direction); True: without them (the backward goes level by level through the per-level entry)
             lse = torch.full((n_tok, H), float("nan"), device=dv) if levels_entry == "lse" else None
             L.call("gdmae_window_attention_levels_fwd", L.ptr(qk), L.ptr(v), L.ptr(out), 1, L.ptr(csr), L.ptr(ws), L.ptr(wl), 3, nw_h, T_h, d, H,
                    L.ptr(tau), 0.01, L.ptr(lse), L.stream())

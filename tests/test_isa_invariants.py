@@ -57,12 +57,12 @@ def test_grouped_weight_gradient_loop_keeps_its_loads_in_flight(tmp_path):
 
 
 @pytest.mark.skipif(shutil.which(HIPCC) is None and not os.path.exists(HIPCC), reason="hipcc not available")
-def test_bf16_rounding_is_the_hardware_instruction(tmp_path):
+def test_bf16_rounding_of_the_one_fused_layer_forward_is_the_hardware_instruction(tmp_path):
     """every bf16 epilogue of the fused layer kernels converts with v_cvt_pk_bf16_f32; the LayerNorm reductions use DPP row
-    operations / permlane swaps, not ds_bpermute shuffles"""
+    operations / permlane swaps, not ds_bpermute shuffles.  There is one forward kernel per width (k_layer_fwd<D>)."""
     k = _isa("layer_fused.hip", tmp_path)
     fwd = sorted(n for n in k if "k_layer_fwdILi256E" in n)
-    assert len(fwd) == 2          # <256, false> (product) and <256, true> (next layer's in-projection on board: GDMAE_QKV_RIDES=1)
+    assert len(fwd) == 1
     for name in fwd:
         text = "\n".join(k[name])
         assert text.count("v_cvt_pk_bf16_f32") >= 32

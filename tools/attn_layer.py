@@ -1,5 +1,5 @@
 """All occupancy levels of one attention call (the entry the layer executor uses) on the bench workload's windows, per stage and
-shift: product path (impl 0: merged workgroup-cooperative launches) against the round-4 per-(window, head) kernels (impl 3)."""
+shift: the product path (merged workgroup-cooperative launches), forward and backward."""
 import logging, os, sys
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [REPO, os.path.join(REPO, "gd-mae_amd")]
@@ -13,7 +13,7 @@ net = build_network(cfg, 3, ds, logging.getLogger("p")).to(dev).train()
 frames = int(os.environ.get("FRAMES", "8"))
 pts = torch.from_numpy(synth.synth_batch(5, frames, ds.point_cloud_range, **skw)).to(dev)
 vox, plan = net.backbone_3d.prefetch_plan(pts, frames).finish()
-tot = {0: [0.0, 0.0], 3: [0.0, 0.0]}
+tot = [0.0, 0.0]
 IDENT = bool(os.environ.get("IDENT"))       # experiment: tokens already in window-major order (csr_tok = identity)
 COLD = bool(os.environ.get("COLD"))         # every timed call behind a 1 GB fill (L2 / MALL hold none of its operands)
 flush = torch.empty(1 << 30, dtype=torch.uint8, device=dev) if COLD else None
@@ -73,25 +73,22 @@ for si, st in enumerate(plan.stages):
             L.call("gdmae_window_attention_levels_bwd", L.ptr(qk), L.ptr(v), L.ptr(g), L.ptr(dqk), L.ptr(dv), 1, L.ptr(part), L.ptr(csr),
                    L.ptr(ws_t), L.ptr(wl_t), nl, nw_h, T_h, d, H, L.ptr(tau), 0.01, L.ptr(out), L.ptr(lse), L.stream())
         line = f"stage {si} shift {shift} windows {w.n_win} tokens {w.n_tok}:"
-        for impl in ((0,) if os.environ.get("NOCSR") else (3, 0)):
-            L.call("gdmae_set_attention_impl", impl)
-            res = []
-            for f in (fwd, bwd):
-                for _ in range(3): f()
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                if COLD:
-                    t = 0.0
-                    for _ in range(8):
-                        flush.fill_(1); e0.record(); f(); e1.record(); torch.cuda.synchronize()
-                        t += e0.elapsed_time(e1)
-                    res.append(t / 8 * 1e3)
-                    continue
-                torch.cuda.synchronize(); e0.record()
-                for _ in range(20): f()
-                e1.record(); torch.cuda.synchronize()
-                res.append(e0.elapsed_time(e1) / 20 * 1e3)
-            tot[impl][0] += res[0]; tot[impl][1] += res[1]
-            line += f"   impl {impl}: fwd {res[0]:6.1f} bwd {res[1]:6.1f} us"
+        res = []
+        for f in (fwd, bwd):
+            for _ in range(3): f()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            if COLD:
+                t = 0.0
+                for _ in range(8):
+                    flush.fill_(1); e0.record(); f(); e1.record(); torch.cuda.synchronize()
+                    t += e0.elapsed_time(e1)
+                res.append(t / 8 * 1e3)
+                continue
+            torch.cuda.synchronize(); e0.record()
+            for _ in range(20): f()
+            e1.record(); torch.cuda.synchronize()
+            res.append(e0.elapsed_time(e1) / 20 * 1e3)
+        tot[0] += res[0]; tot[1] += res[1]
+        line += f"   fwd {res[0]:6.1f} bwd {res[1]:6.1f} us"
         print(line)
-L.call("gdmae_set_attention_impl", 0)
-print("per step (2 layers per shift and stage):", {k: [round(2 * x, 1) for x in v] for k, v in tot.items()})
+print("per step (2 layers per shift and stage):", [round(2 * x, 1) for x in tot])

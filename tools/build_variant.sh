@@ -7,7 +7,7 @@ name=$1; src=$2; shift 2
 cd "$(dirname "$0")/../gd-mae_amd/csrc"
 mkdir -p variants
 extra=""
-case $src in attention_t32.hip|attention_t16.hip|vfe_fused.hip|vfe_layer2.hip) extra="-mllvm -amdgpu-mfma-vgpr-form=1";; esac
+case $src in attention_t16.hip|attention_coop.hip|vfe_fused.hip|vfe_layer2.hip) extra="-mllvm -amdgpu-mfma-vgpr-form=1";; esac
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -Wno-unused-result $extra "$@" -c $src -o variants/${name}_${src%.hip}.o
 objs=$(ls *.o | grep -v "^${src%.hip}.o$")
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o variants/lib_${name}.so $objs variants/${name}_${src%.hip}.o -L/opt/rocm/lib -lhipblaslt

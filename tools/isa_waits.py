@@ -7,7 +7,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 src = sys.argv[1]
 out = "/tmp/_isa_%s.s" % os.path.basename(src).replace(".hip", "")
 extra = sys.argv[2:]
-if src.split("/")[-1] in ("attention_t32.hip", "attention_t16.hip", "vfe_fused.hip", "vfe_layer2.hip"):
+if src.split("/")[-1] in ("attention_t16.hip", "attention_coop.hip", "vfe_fused.hip", "vfe_layer2.hip"):
     extra += ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]
 cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-Wno-unused-result"] + extra + ["-S", "--cuda-device-only", "-o", out, src]
 subprocess.run(cmd, cwd=os.path.join(REPO, "gd-mae_amd", "csrc"), check=True, stderr=subprocess.DEVNULL)
