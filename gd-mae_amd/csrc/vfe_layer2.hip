@@ -5,16 +5,16 @@
 // 16-bit throughput mode only (y1 is the bf16 - or, round 6, fp16 - output of gdmae_vfe_point_layer_fwd; the fp32 parity mode keeps the
 // op-by-op path).  F16 instantiations (gdmae_vfe_max_layer_*_f16): y1 holds fp16 values and W arrives as the fp32 master matrix, rounded
 // to fp16 for the pre-activation h = y1 W^T (v_mfma_f32_32x32x16_f16) and to bf16 for the gradient product dy1 = dx W; y1^T is converted
-// to bf16 when k_v2_dw stages it.  Why: the pillar maximum passes ONE point's value on - the rounding of y1 and of W does not average
+// to bf16 when k_v2_dydw stages it.  Why: the pillar maximum passes ONE point's value on - the rounding of y1 and of W does not average
 // over a pillar's points - and DynVFE in bf16 was the largest term of config E's small-case loss scatter.  h (N x 128, 366 MB in bf16 for an 8-frame batch) is never stored: a 32-point tile of it is
 // 16 v_mfma_f32_32x32x16_bf16 from a 4 KB tile of y1, so every kernel below recomputes it in accumulators:
 //   forward   k_v2_stats  : column sums of h, h^2 (fp32 accumulators)  -> gd_bn_fold_from_partials
 //             k_v2_max    : tiles in pillar (CSR) order; the tile goes through LDS and each lane walks one column
 //   (see k_v2_max below)    a pillar is closed whenever the pillar id changes -> out, arg
 //   backward  k_v2_gstats : gm = g [out > 0], column sums of gm, gm*h(arg) with h(arg) = (out - b) / a
-//             k_v2_dy     : dx = a dh + c0 + c1 h  (dh = gm at the arg-max point) -> LDS -> dy1 = dx W  (MFMA)
-//             k_v2_dw     : dW^T += y1^T dx, the dx accumulators are the B operand, y1^T comes from a transposed
-//                           LDS tile; per-workgroup partials, fixed-order reduction
+//             k_v2_dydw   : dx = a dh + c0 + c1 h  (dh = gm at the arg-max point), once per tile, feeds both products:
+//                           dy1 = dx W (dx through a shared LDS tile) and dW^T += y1^T dx (the dx accumulators are the B
+//                           operand, y1^T comes from a transposed LDS tile; per-workgroup partials, fixed-order reduction)
 // Accumulator layout of v_mfma_f32_32x32x16: lane (n = lane % 32, half = lane / 32) holds column n, register r holds
 // row (r & 3) + 8 (r >> 2) + 4 half.
 #include "common.h"
@@ -43,14 +43,6 @@ union V2Frag {
   unsigned short s[8];
 };
 
-#ifndef V2_DW_WPE
-#define V2_DW_WPE 0
-#endif
-#if V2_DW_WPE
-#define V2_DW_ATTR __attribute__((amdgpu_waves_per_eu(V2_DW_WPE, V2_DW_WPE)))
-#else
-#define V2_DW_ATTR
-#endif
 constexpr int V2_CI = 64, V2_CO = 128;
 constexpr int V2_WAVES = 4;
 constexpr int V2_LDW = V2_CI + 8;     // bf16 elements per row of the W tile (128 x 64) in LDS
@@ -71,11 +63,6 @@ __device__ __forceinline__ bf16x8 v2_pack(const f32x16& a, int r0) {   // 8 accu
 #pragma unroll
   for (int j = 0; j < 8; ++j) t[j] = a[r0 + j];
   return __builtin_convertvector(t, bf16x8);
-}
-__device__ __forceinline__ void v2_wave_sync() {   // LDS written and read by the same wave: ordering only
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 // W (128, 64) -> LDS, rows padded to V2_LDW.  F16: W is the fp32 master matrix, rounded to fp16 here; else bf16, copied
@@ -421,9 +408,9 @@ __device__ __forceinline__ f32x16 v2_dx(const f32x16& h, const V2Coef& k, const 
   int am[16];
 #pragma unroll
   for (int r = 0; r < 16; ++r) {          // 32 independent loads; the rows of a pillar are adjacent and share cache lines
-    const long long o = (long long)prow[r] * V2_CO + c;
-    am[r] = arg[o];
-    gv[r] = gm[o];
+    const unsigned o = ((unsigned)prow[r] * V2_CO + c) * 4u;      // byte offset: M * 512 < 2^32 (checked by the caller)
+    am[r] = *reinterpret_cast<const int*>(reinterpret_cast<const char*>(arg) + o);
+    gv[r] = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(gm) + o);
   }
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
@@ -433,91 +420,33 @@ __device__ __forceinline__ f32x16 v2_dx(const f32x16& h, const V2Coef& k, const 
   return dx;
 }
 
-// ---- backward: dy1 = dx W ------------------------------------------------------------------------------------------
+// ---- backward: dy1 = dx W and dW = dx^T y1 in one pass over the rows ------------------------------------------------
+// One workgroup per 32-row tile.  Wave w owns the 32 columns [32 w, 32 w + 32) of the tile's h and dx - one quarter of the (arg, gm)
+// gathers, 4 MFMAs - and the same rows of dW^T (acc[2], the dx accumulators are the B operand; y1^T comes from the shared transposed
+// tile sT, each wave stages 16 of its 64 channels before its gathers, so that the y1 fragments are dead while they are in flight).
+// Its bf16 dx block also goes into the shared row-major tile sX; behind the workgroup barrier two of the four waves (alternating
+// from tile to tile) multiply the whole tile by W^T: each owns 32 of the 64 input channels, 8 MFMAs in the k order 0 .. 127 - every
+// dy1 element is the same chain of products as in a wave-per-tile kernel, whichever lane holds it.  dW leaves as per-workgroup
+// partials for the fixed-order reduction.  LDS 49 664 bytes and 159 / 161 registers (bf16 / fp16 rows): three workgroups per CU, the
+// grid k_v2_dw had - with the same tiles per workgroup dW is bit-identical to the two-kernel form.  (64-bit gather addresses in v2_dx
+// cost 9 - 11 registers more: the fp16 instantiation then misses the 168 of three waves per SIMD.)
 template <bool F16>
-__global__ __launch_bounds__(V2_WAVES * 64) void k_v2_dy(const unsigned short* __restrict__ y1, long long N,
-                                                         const void* __restrict__ W, const int* __restrict__ rowpil,
-                                                         const float* __restrict__ ab, const float* __restrict__ c01,
-                                                         const int* __restrict__ arg, const float* __restrict__ gm,
-                                                         unsigned* __restrict__ dy1) {
+__global__ __launch_bounds__(V2_WAVES * 64) void k_v2_dydw(const unsigned short* __restrict__ y1, long long N,
+                                                           const void* __restrict__ W, const int* __restrict__ rowpil,
+                                                           const float* __restrict__ ab, const float* __restrict__ c01,
+                                                           const int* __restrict__ arg, const float* __restrict__ gm,
+                                                           unsigned* __restrict__ dy1, float* __restrict__ part) {
   __shared__ unsigned short sW[V2_CO * V2_LDW];
-  __shared__ unsigned short sWT[V2_CI * V2_LDX];            // W^T: row j (input channel), column c
-  __shared__ unsigned short sX[V2_WAVES * 32 * V2_LDX];     // per wave: the bf16 dx tile, row-major
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n = lane & 31, half = lane >> 5;
+  __shared__ unsigned short sWT[V2_CI * V2_LDX];   // W^T: row j (input channel), column c
+  __shared__ unsigned short sX[32 * V2_LDX];       // the tile's bf16 dx, row-major
+  __shared__ unsigned short sT[V2_CI * V2_LDT];    // the tile's y1 transposed: row j, column = tile row
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), n = lane & 31, half = lane >> 5;
   v2_load_w<F16>(W, sW);
   for (int q = threadIdx.x; q < V2_CO * V2_CI; q += V2_WAVES * 64) {      // W^T in bf16: operand of the gradient product
     const int c = q >> 6, j = q & 63;
     sWT[j * V2_LDX + c] = F16 ? v2_f2bf(((const float*)W)[q]) : ((const unsigned short*)W)[q];
   }
   __syncthreads();
-  unsigned short* sx = sX + wave * 32 * V2_LDX;
-  V2Coef k[4];
-#pragma unroll
-  for (int b = 0; b < 4; ++b) {
-    const int c = 32 * b + n;
-    k[b].a = ab[c]; k[b].c0 = c01[c]; k[b].c1 = c01[V2_CO + c];
-  }
-  const long long ntiles = (N + 31) / 32;
-  const long long stride = (long long)gridDim.x * V2_WAVES;
-  long long t = (long long)blockIdx.x * V2_WAVES + wave;
-  V2Frag ya[4], yn[4];
-  int pil = 0, piln = 0;
-  if (t < ntiles) v2_load_tile(y1, rowpil, t, N, n, half, ya, pil);
-  for (; t < ntiles; t += stride) {
-    const long long q = t * 32;
-    const int nrows = (int)(N - q < 32 ? N - q : 32);
-    if (t + stride < ntiles) v2_load_tile(y1, rowpil, t + stride, N, n, half, yn, piln);   // in flight during this tile
-    int prow[16];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) prow[r] = __shfl(pil, v2_row(r, half), 64);
-#pragma unroll
-    for (int b = 0; b < 4; ++b) {
-      const f32x16 h = v2_h<F16>(ya, sW, n, half, b);
-      const f32x16 dx = v2_dx(h, k[b], arg, gm, 32 * b + n, prow, (int)q, half);
-#pragma unroll
-      for (int r = 0; r < 16; ++r) sx[v2_row(r, half) * V2_LDX + 32 * b + n] = v2_f2bf(dx[r]);
-      __builtin_amdgcn_sched_barrier(0);      // one block at a time: keeps the register count at 3 waves per SIMD
-    }
-    v2_wave_sync();
-    // D[i = row][j = input channel 2 n + blk] = sum_c dx[row][c] W[c][j]
-    f32x16 d[2];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) d[0][r] = d[1][r] = 0.f;
-#pragma unroll
-    for (int s = 0; s < 8; ++s) {
-      V2Frag a, b0, b1;
-      a.u = *reinterpret_cast<const uint4*>(sx + n * V2_LDX + 16 * s + 8 * half);
-      b0.u = *reinterpret_cast<const uint4*>(sWT + (2 * n) * V2_LDX + 16 * s + 8 * half);
-      b1.u = *reinterpret_cast<const uint4*>(sWT + (2 * n + 1) * V2_LDX + 16 * s + 8 * half);
-      d[0] = v2_mfma(a.v, b0.v, d[0]);
-      d[1] = v2_mfma(a.v, b1.v, d[1]);
-    }
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      if (v2_row(r, half) < nrows)
-        dy1[(q + v2_row(r, half)) * (V2_CI / 2) + n] = (unsigned)v2_f2bf(d[0][r]) | ((unsigned)v2_f2bf(d[1][r]) << 16);
-    }
-    v2_wave_sync();
-    pil = piln;
-#pragma unroll
-    for (int s = 0; s < 4; ++s) ya[s] = yn[s];
-  }
-}
-
-// ---- backward: dW = dx^T y1 ----------------------------------------------------------------------------------------
-// the four waves of a workgroup share each tile, wave w owns the 32 columns [32 w, 32 w + 32) of dx / rows of dW
-template <bool F16>
-__global__ __launch_bounds__(V2_WAVES * 64) V2_DW_ATTR void k_v2_dw(const unsigned short* __restrict__ y1, long long N,
-                                                         const void* __restrict__ W, const int* __restrict__ rowpil,
-                                                         const float* __restrict__ ab, const float* __restrict__ c01,
-                                                         const int* __restrict__ arg, const float* __restrict__ gm,
-                                                         float* __restrict__ part) {
-  __shared__ unsigned short sW[V2_CO * V2_LDW];
-  __shared__ unsigned short sT[V2_WAVES * V2_CI * V2_LDT];   // per wave: y1 tile transposed, row j, column = tile row
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n = lane & 31, half = lane >> 5;
-  v2_load_w<F16>(W, sW);
-  __syncthreads();
-  unsigned short* st = sT + wave * V2_CI * V2_LDT;
   const int b = wave, c = 32 * b + n;
   V2Coef k;
   k.a = ab[c]; k.c0 = c01[c]; k.c1 = c01[V2_CO + c];
@@ -529,34 +458,66 @@ __global__ __launch_bounds__(V2_WAVES * 64) V2_DW_ATTR void k_v2_dw(const unsign
   V2Frag ya[4], yn[4];
   int pil = 0, piln = 0;
   if (t < ntiles) v2_load_tile(y1, rowpil, t, N, n, half, ya, pil);   // rows past the end are zero: nothing added to dW
-  for (; t < ntiles; t += gridDim.x) {
+  for (int it = 0; t < ntiles; t += gridDim.x, ++it) {
     const long long q = t * 32;
+    const int nrows = (int)(N - q < 32 ? N - q : 32);
     if (t + gridDim.x < ntiles) v2_load_tile(y1, rowpil, t + gridDim.x, N, n, half, yn, piln);
+    __syncthreads();                   // the previous tile's readers are done
 #pragma unroll
     for (int s = 0; s < 4; ++s)
+      if (s == wave) {                 // (F16: the transposed tile is the bf16 operand of the gradient product with dx)
 #pragma unroll
-      for (int j = 0; j < 8; ++j)      // (F16: the transposed tile is the bf16 operand of the gradient product with dx)
-        st[(16 * s + 8 * half + j) * V2_LDT + n] = F16 ? v2_f2bf((float)ya[s].hv[j]) : ya[s].s[j];
+        for (int j = 0; j < 8; ++j) sT[(16 * s + 8 * half + j) * V2_LDT + n] = F16 ? v2_f2bf((float)ya[s].hv[j]) : ya[s].s[j];
+      }
     int prow[16];
 #pragma unroll
     for (int r = 0; r < 16; ++r) prow[r] = __shfl(pil, v2_row(r, half), 64);
     const f32x16 h = v2_h<F16>(ya, sW, n, half, b);
-    const f32x16 dx = v2_dx(h, k, arg, gm, c, prow, (int)q, half);
-    v2_wave_sync();
+    V2Frag bx[2];                      // dx in bf16: registers [8 kk, 8 kk + 8) of the accumulator layout
+    {
+      const f32x16 dx = v2_dx(h, k, arg, gm, c, prow, (int)q, half);
+      bx[0].v = v2_pack(dx, 0);
+      bx[1].v = v2_pack(dx, 8);
+    }
+#pragma unroll
+    for (int r = 0; r < 16; ++r) sX[v2_row(r, half) * V2_LDX + c] = bx[r >> 3].s[r & 7];
+    __syncthreads();
     // A fragments of D[i = channel][j = column] = sum_rows y1[row][channel] dx[row][column]: channel 32 i2 + n, the 8 rows
     // base + 4 half + {0..3}, base + 8 + 4 half + {0..3} - the rows of accumulator registers [base / 2, base / 2 + 8)
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk) {
-      const bf16x8 bx = v2_pack(dx, 8 * kk);
 #pragma unroll
       for (int i2 = 0; i2 < 2; ++i2) {
         V2Frag at;
-        at.u2[0] = *reinterpret_cast<const uint2*>(st + (32 * i2 + n) * V2_LDT + 16 * kk + 4 * half);
-        at.u2[1] = *reinterpret_cast<const uint2*>(st + (32 * i2 + n) * V2_LDT + 16 * kk + 8 + 4 * half);
-        acc[i2] = v2_mfma(at.v, bx, acc[i2]);
+        at.u2[0] = *reinterpret_cast<const uint2*>(sT + (32 * i2 + n) * V2_LDT + 16 * kk + 4 * half);
+        at.u2[1] = *reinterpret_cast<const uint2*>(sT + (32 * i2 + n) * V2_LDT + 16 * kk + 8 + 4 * half);
+        acc[i2] = v2_mfma(at.v, bx[kk].v, acc[i2]);
       }
     }
-    v2_wave_sync();
+    if ((wave >> 1) == (it & 1)) {
+      // D[i = row][j = input channel 32 u + n] = sum_c dx[row][c] W[c][j]
+      const int j = 32 * (wave & 1) + n;
+      f32x16 d;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) d[r] = 0.f;
+#pragma unroll
+      for (int s = 0; s < 8; ++s) {
+        V2Frag a, w;
+        a.u = *reinterpret_cast<const uint4*>(sX + n * V2_LDX + 16 * s + 8 * half);
+        w.u = *reinterpret_cast<const uint4*>(sWT + j * V2_LDX + 16 * s + 8 * half);
+        d = v2_mfma(a.v, w.v, d);
+      }
+      // registers r, r + 1 are adjacent rows; neighbouring lanes swap one of them, so that every lane stores one channel pair
+      // (4 bytes) of one row: the even lane of row(r), the odd lane of row(r + 1)
+      const bool odd = n & 1;
+#pragma unroll
+      for (int r = 0; r < 16; r += 2) {
+        const unsigned lo = v2_f2bf(d[r]), hi = v2_f2bf(d[r + 1]);
+        const unsigned got = (unsigned)__shfl_xor((int)(odd ? lo : hi), 1, 64);
+        const int row = v2_row(r, half) + (odd ? 1 : 0);
+        if (row < nrows) dy1[(q + row) * (V2_CI / 2) + (j >> 1)] = odd ? (got | (hi << 16)) : (lo | (got << 16));
+      }
+    }
     pil = piln;
 #pragma unroll
     for (int s = 0; s < 4; ++s) ya[s] = yn[s];
@@ -570,7 +531,7 @@ __global__ __launch_bounds__(V2_WAVES * 64) V2_DW_ATTR void k_v2_dw(const unsign
 
 template <typename K>
 int v2_resident_blocks(K kernel, int slot, int cap) {
-  static int cache[8] = {0};
+  static int cache[6] = {0};
   if (cache[slot] == 0) {
     int per_cu = 0, dev = 0;
     hipDeviceProp_t prop;
@@ -623,7 +584,7 @@ static int v2_fwd(const void* y1, long long N, const void* W, const int* pillar_
   GD_REQUIRE(N > 0 && M > 0, "vfe max layer: no points");
   hipStream_t st = (hipStream_t)stream;
   const V2Ws ws = v2_ws(workspace);
-  const int g1 = v2_grid(N, v2_resident_blocks(k_v2_stats<F16>, F16 ? 4 : 0, V2_MAX_GRID));
+  const int g1 = v2_grid(N, v2_resident_blocks(k_v2_stats<F16>, F16 ? 3 : 0, V2_MAX_GRID));
   hipLaunchKernelGGL(k_v2_stats<F16>, dim3(g1), dim3(V2_WAVES * 64), 0, st, (const unsigned short*)y1, N, W, ws.part);
   GD_LAUNCH_CHECK();
   int rc = gd_bn_fold_from_partials(st, ws.part, g1, V2_CO, (double)N, gamma, beta, eps, momentum, running_mean, running_var,
@@ -631,7 +592,7 @@ static int v2_fwd(const void* y1, long long N, const void* W, const int* pillar_
   if (rc) return rc;
   // boundary pieces of k_v2_max: 2 slots x 128 columns x (value, row) per worker, in the partial area (the statistics partials have
   // been consumed by the fold above): V2_MAXW_GRID workgroups x 8 workers x 2 KB = the area's 32 MB
-  const int g2 = v2_grid(N, v2_resident_blocks(k_v2_max<F16>, F16 ? 5 : 1, V2_MAXW_GRID));
+  const int g2 = v2_grid(N, v2_resident_blocks(k_v2_max<F16>, F16 ? 4 : 1, V2_MAXW_GRID));
   const long long nwk = (long long)g2 * V2_WAVES * 2, per = (N + nwk - 1) / nwk;
   float* const pbest = ws.part;
   int* const parg = (int*)(ws.part + nwk * 2 * V2_CO);
@@ -667,6 +628,7 @@ static int v2_bwd(const void* y1, long long N, const void* W, const int* row_pil
                   const float* ab, const float* out, const int* arg, const float* g, void* gm, void* dy1, float* dgamma, float* dbeta,
                   float* dW, int accumulate, void* workspace, void* stream) {
   GD_REQUIRE(N > 0 && M > 0, "vfe max layer: no points");
+  GD_REQUIRE(M < (1 << 23), "vfe max layer: the (arg, gm) gathers use 32-bit byte offsets");
   hipStream_t st = (hipStream_t)stream;
   const V2Ws ws = v2_ws(workspace);
   int g0 = (int)(M / 64 > V2_MAX_GRID ? V2_MAX_GRID : (M / 64 > 0 ? M / 64 : 1));
@@ -676,14 +638,10 @@ static int v2_bwd(const void* y1, long long N, const void* W, const int* row_pil
   if (rc) return rc;
   rc = gdmae_bn_bwd_coeffs(ws.sums, 2, stats, ab, gamma, V2_CO, (double)N, nullptr, dgamma, dbeta, accumulate, ws.c01, stream);
   if (rc) return rc;
-  const int g1 = v2_grid(N, v2_resident_blocks(k_v2_dy<F16>, F16 ? 6 : 2, 4096));
-  hipLaunchKernelGGL(k_v2_dy<F16>, dim3(g1), dim3(V2_WAVES * 64), 0, st, (const unsigned short*)y1, N, W, row_pillar, (const float*)ab,
-                     (const float*)ws.c01, arg, (const float*)gm, (unsigned*)dy1);
-  GD_LAUNCH_CHECK();
-  int g2 = v2_resident_blocks(k_v2_dw<F16>, F16 ? 7 : 3, V2_DW_GRID);     // one tile per workgroup and iteration
+  int g2 = v2_resident_blocks(k_v2_dydw<F16>, F16 ? 5 : 2, V2_DW_GRID);   // one tile per workgroup and iteration; one partial tile each
   if (g2 > (N + 31) / 32) g2 = (int)((N + 31) / 32);
-  hipLaunchKernelGGL(k_v2_dw<F16>, dim3(g2), dim3(V2_WAVES * 64), 0, st, (const unsigned short*)y1, N, W, row_pillar, (const float*)ab,
-                     (const float*)ws.c01, arg, (const float*)gm, ws.part);
+  hipLaunchKernelGGL(k_v2_dydw<F16>, dim3(g2), dim3(V2_WAVES * 64), 0, st, (const unsigned short*)y1, N, W, row_pillar, (const float*)ab,
+                     (const float*)ws.c01, arg, (const float*)gm, (unsigned*)dy1, ws.part);
   GD_LAUNCH_CHECK();
   return gd_splitk_acc(st, ws.part, g2, (long long)V2_CO * V2_CI, dW, accumulate);
 }
