@@ -125,7 +125,9 @@ struct CdArgs {
 
 // OF32: the accumulators (+ bias) leave as fp32 rows, optionally added to the map's previous content - the building block of the
 // fp32-grade convolution of the parity mode (three launches on the bf16 value / remainder splits of both operands, conv3x3_f32)
-template <int CIB, int CO, int DIL, bool OF32>
+// RELU (bf16 output only): Y = relu(conv + bias) (+ addend after the ReLU) - a Conv-BatchNorm(eval)-ReLU block with the affine folded
+// into the weights and the bias, and the identity shortcut of SSTBEVBackbone added in the store pass
+template <int CIB, int CO, int DIL, bool OF32, bool RELU = false>
 __global__ __launch_bounds__(256, 2) void k_conv3x3_dense(CdArgs A) {
   using Gm = CdGeom<CIB, DIL>;
   constexpr int PW = Gm::PW, SITE = Gm::SITE, ROW = Gm::ROW, TILE = Gm::TILE, KS = Gm::KS;
@@ -267,8 +269,13 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_dense(CdArgs A) {
                 make_float4(a[4 * j] + bv[4 * j], a[4 * j + 1] + bv[4 * j + 1], a[4 * j + 2] + bv[4 * j + 2], a[4 * j + 3] + bv[4 * j + 3]);
           } else {
             uint2 o;
+            if constexpr (RELU) {
+              o.x = cd_pack2(fmaxf(a[4 * j] + bv[4 * j], 0.f), fmaxf(a[4 * j + 1] + bv[4 * j + 1], 0.f));
+              o.y = cd_pack2(fmaxf(a[4 * j + 2] + bv[4 * j + 2], 0.f), fmaxf(a[4 * j + 3] + bv[4 * j + 3], 0.f));
+            } else {
             o.x = cd_pack2(a[4 * j] + bv[4 * j], a[4 * j + 1] + bv[4 * j + 1]);
             o.y = cd_pack2(a[4 * j + 2] + bv[4 * j + 2], a[4 * j + 3] + bv[4 * j + 3]);
+            }
             *reinterpret_cast<uint2*>(lds + site * SP + (c0 + 8 * j) * 2) = o;
           }
         }
@@ -368,20 +375,20 @@ __global__ __launch_bounds__(256) void k_cd_stats_prereduce(const float* __restr
   }
 }
 
-template <int CIB, int CO, int DIL, bool OF32>
+template <int CIB, int CO, int DIL, bool OF32, bool RELU = false>
 int cd_launch(const CdArgs& A, hipStream_t st) {
   using Gm = CdGeom<CIB, DIL>;
   constexpr int patch = 2 * Gm::TILE, stg = 128 * (CO * (OF32 ? 4 : 2) + 16);
   constexpr int lds = patch > stg ? patch : stg;
   static bool once = false;
   if (!once) {
-    GD_CHECK(hipFuncSetAttribute((const void*)k_conv3x3_dense<CIB, CO, DIL, OF32>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    GD_CHECK(hipFuncSetAttribute((const void*)k_conv3x3_dense<CIB, CO, DIL, OF32, RELU>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     once = true;
   }
   CdArgs B_ = A;
   B_.ncb = A.cout / CO;
   const unsigned ntp8 = (unsigned)gd_div_up(gd_div_up(A.n_tiles, 2), 8) * 8;           // tile pairs, padded to the XCD count
-  hipLaunchKernelGGL((k_conv3x3_dense<CIB, CO, DIL, OF32>), dim3(ntp8 * (unsigned)B_.ncb), dim3(256), lds, st, B_);
+  hipLaunchKernelGGL((k_conv3x3_dense<CIB, CO, DIL, OF32, RELU>), dim3(ntp8 * (unsigned)B_.ncb), dim3(256), lds, st, B_);
   GD_LAUNCH_CHECK();
   return 0;
 }
@@ -605,17 +612,19 @@ extern "C" int gdmae_conv3x3_dense_pack(const float* weight, int cin, int cout, 
 // (the padded counts of gdmae_conv3x3_dense_pack; for the input gradient the roles of the layer's cin / cout are swapped).
 // out_f32 = 0: Y bf16; 1: Y fp32, added to its previous content when accumulate != 0.
 static int cd_conv(const void* X, int B, int H, int W, int cin_l, int cout_l, int dil, const void* packed, const float* bias, void* Y, int out_f32,
-                   int accumulate, void* stream, float* stat_ws = nullptr, const void* addend = nullptr) {
+                   int accumulate, void* stream, float* stat_ws = nullptr, const void* addend = nullptr, bool relu = false) {
   GD_REQUIRE(cin_l % 32 == 0 && cout_l % 32 == 0 && cd_shape_ok(cin_l, cout_l, dil), "conv3x3_dense: channel counts must be multiples of 32");
   if (B <= 0 || H <= 0 || W <= 0) return 0;
   const int cib = cd_cib(cin_l, dil), co = cd_co(cout_l);
   CdArgs A{(const unsigned short*)X, (const uint4*)packed, bias, (unsigned short*)Y, B, H, W, (H + 7) / 8, (W + 7) / 8, cin_l, cout_l,
            cin_l / cib, cout_l / 32, 0, accumulate, 1, stat_ws, (const unsigned short*)addend};
   GD_REQUIRE(addend == nullptr || (!out_f32 && stat_ws == nullptr), "conv3x3_dense: an addend goes with a plain bf16 output");
+  GD_REQUIRE(!relu || (!out_f32 && stat_ws == nullptr), "conv3x3_dense: the ReLU epilogue goes with a plain bf16 output");
   A.n_tiles = B * A.TH * A.TW;
   hipStream_t st = (hipStream_t)stream;
 #define CD_CASE(ci, c, d) \
-  if (cib == ci && co == c && dil == d) return out_f32 ? cd_launch<ci, c, d, true>(A, st) : cd_launch<ci, c, d, false>(A, st);
+  if (cib == ci && co == c && dil == d)    \
+    return out_f32 ? cd_launch<ci, c, d, true>(A, st) : (relu ? cd_launch<ci, c, d, false, true>(A, st) : cd_launch<ci, c, d, false>(A, st));
   CD_CASE(64, 128, 1)
   CD_CASE(64, 64, 1)
   CD_CASE(64, 32, 1)
@@ -637,6 +646,13 @@ extern "C" int gdmae_conv3x3_dense_add(const void* X, int B, int H, int W, int c
                                        const void* addend, void* Y, void* stream) {
   GD_REQUIRE(addend != nullptr, "conv3x3_dense_add: addend");
   return cd_conv(X, B, H, W, cin_l, cout_l, dil, packed, bias, Y, 0, 0, stream, nullptr, addend);
+}
+// Y = bf16(relu(conv(X) + bias)) (+ shortcut (B, H, W, cout_l) bf16 or NULL, added to the rounded value and rounded again - the order of
+// a Conv-BatchNorm-ReLU block followed by an identity shortcut, sst_bev_backbone.py:36-40): the block in evaluation mode with the
+// BatchNorm's running-statistics affine folded into the packed weights and the bias
+extern "C" int gdmae_conv3x3_dense_relu(const void* X, int B, int H, int W, int cin_l, int cout_l, int dil, const void* packed, const float* bias,
+                                        const void* shortcut, void* Y, void* stream) {
+  return cd_conv(X, B, H, W, cin_l, cout_l, dil, packed, bias, Y, 0, 0, stream, nullptr, shortcut, true);
 }
 // ... + the BatchNorm statistics of the layer that follows: stat_rows (GDMAE_CD_STAT_ROWS = 256, 2, cout_l) fp32 partial rows of the
 // per-channel sum / sum of squares of the rounded outputs over all B H W sites (the format gdmae_bn_fold_partials takes) - the epilogue

@@ -48,6 +48,7 @@ struct SpArgs {
   float* ride_dW;
   int ride_S, ride_cout, ride_cin;
   unsigned ride_blocks;
+  const float* bias;      // EPI instantiations only: (COUT) fp32, Y = relu(acc + bias) - the folded BatchNorm(eval) + ReLU of a conv block
 };
 
 __device__ __forceinline__ void sp_ride_dw_reduce(const SpArgs& A) {
@@ -94,7 +95,8 @@ struct SpRows {
   static constexpr int value = COUT >= 256 ? ((SRC_F32 && CIN >= 256) ? 32 : SP_ROWS256) : ((CIN == 128 && !SRC_F32) ? SP_ROWS128 : 64);
 };
 
-template <int CIN, int COUT, bool SRC_F32>
+// EPI: the inference epilogue relu(acc + bias) (no statistics, no rider); false: the training instantiations, unchanged
+template <int CIN, int COUT, bool SRC_F32, bool EPI = false>
 __global__ __launch_bounds__(512, 2) void k_spconv(SpArgs A) {
   constexpr int ROWS = SpRows<CIN, COUT, SRC_F32>::value;
   constexpr int KS = CIN / 16;                     // k-steps per tap
@@ -245,8 +247,14 @@ __global__ __launch_bounds__(512, 2) void k_spconv(SpArgs A) {
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         uint2 o;
+        if constexpr (EPI) {
+          const float4 bv = *reinterpret_cast<const float4*>(A.bias + cb + 8 * q);
+          o.x = sp_pack2(fmaxf(acc[j][b][4 * q] + bv.x, 0.f), fmaxf(acc[j][b][4 * q + 1] + bv.y, 0.f));
+          o.y = sp_pack2(fmaxf(acc[j][b][4 * q + 2] + bv.z, 0.f), fmaxf(acc[j][b][4 * q + 3] + bv.w, 0.f));
+        } else {
         o.x = sp_pack2(acc[j][b][4 * q], acc[j][b][4 * q + 1]);
         o.y = sp_pack2(acc[j][b][4 * q + 2], acc[j][b][4 * q + 3]);
+        }
         *reinterpret_cast<uint2*>(lds + row * SP + (cb + 8 * q) * 2) = o;
       }
     }
@@ -299,17 +307,17 @@ __global__ __launch_bounds__(512, 2) void k_spconv(SpArgs A) {
   }
 }
 
-template <int CIN, int COUT, bool SRC_F32>
+template <int CIN, int COUT, bool SRC_F32, bool EPI = false>
 int sp_launch(const SpArgs& A, hipStream_t st) {
   constexpr int ROWS = SpRows<CIN, COUT, SRC_F32>::value;
   constexpr int tile = ROWS * (CIN * 2 + 16), stg = ROWS * (COUT * 2 + 16);
   constexpr int lds = 2 * tile > stg ? 2 * tile : stg;
   static bool once = false;
   if (!once) {
-    GD_CHECK(hipFuncSetAttribute((const void*)k_spconv<CIN, COUT, SRC_F32>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    GD_CHECK(hipFuncSetAttribute((const void*)k_spconv<CIN, COUT, SRC_F32, EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     once = true;
   }
-  hipLaunchKernelGGL((k_spconv<CIN, COUT, SRC_F32>), dim3((unsigned)gd_div_up(A.n, ROWS) + A.ride_blocks), dim3(512), lds, st, A);
+  hipLaunchKernelGGL((k_spconv<CIN, COUT, SRC_F32, EPI>), dim3((unsigned)gd_div_up(A.n, ROWS) + A.ride_blocks), dim3(512), lds, st, A);
   GD_LAUNCH_CHECK();
   return 0;
 }
@@ -338,7 +346,7 @@ int gd_spconv(hipStream_t st, const void* X, int x_f32, const int* nbr, const vo
               float* part, const float* ride_part, int ride_S, int ride_cout, int ride_cin, float* ride_dW) {
   if (n <= 0) return ride_part ? -2 : 0;
   GD_REQUIRE(gd_spconv_supported(cin, cout), "spconv: channels must be 128 or 256");
-  SpArgs A{X, nbr, (const uint4*)Wp, (unsigned short*)Y, n, part, nullptr, nullptr, 0, 0, 0, 0u};
+  SpArgs A{X, nbr, (const uint4*)Wp, (unsigned short*)Y, n, part, nullptr, nullptr, 0, 0, 0, 0u, nullptr};
   if (ride_part) {
     A.ride_part = ride_part; A.ride_dW = ride_dW; A.ride_S = ride_S; A.ride_cout = ride_cout; A.ride_cin = ride_cin;
     A.ride_blocks = (unsigned)gd_div_up(9ll * ride_cout * ride_cin / 4, 512);
@@ -377,6 +385,24 @@ extern "C" int gdmae_spconv_pack_jobs(const float* W, int cin, int cout, int tra
 extern "C" int gdmae_spconv(const void* X, int x_f32, const int* nbr, const void* packed, long long n, int cin, int cout, void* Y,
                             int timing_slot, void* stream) {
   return gd_spconv((hipStream_t)stream, X, x_f32, nbr, packed, n, cin, cout, Y, timing_slot > 0 ? timing_slot : GD_T_SPCONV_FWD, nullptr, nullptr, 0, 0, 0, nullptr);
+}
+// Y = relu(sum_tap W'_tap X[nbr[:, tap]] + bias): a conv block in evaluation mode, BatchNorm folded into W' / bias by the caller
+extern "C" int gdmae_spconv_bias_relu(const void* X, int x_f32, const int* nbr, const void* packed, const float* bias, long long n, int cin,
+                                      int cout, void* Y, void* stream) {
+  if (n <= 0) return 0;
+  GD_REQUIRE(gd_spconv_supported(cin, cout), "spconv_bias_relu: channels must be 128 or 256");
+  GD_REQUIRE(bias != nullptr, "spconv_bias_relu: bias");
+  hipStream_t st = (hipStream_t)stream;
+  SpArgs A{X, nbr, (const uint4*)packed, (unsigned short*)Y, n, nullptr, nullptr, nullptr, 0, 0, 0, 0u, bias};
+  GdTimed timed(GD_T_SPCONV_FWD, st, (double)n * (9.0 * cin * (x_f32 ? 4 : 2) + 2.0 * cout + 36.0) + 18.0 * cin * cout, 2.0 * n * 9.0 * cin * cout);
+#define SP_CASE(ci, co) \
+  if (cin == ci && cout == co) return x_f32 ? sp_launch<ci, co, true, true>(A, st) : sp_launch<ci, co, false, true>(A, st);
+  SP_CASE(128, 128);
+  SP_CASE(128, 256);
+  SP_CASE(256, 128);
+  SP_CASE(256, 256);
+#undef SP_CASE
+  return -1;
 }
 extern "C" int gdmae_spconv_stat_rows(int cin, int cout, int x_f32) { return gd_spconv_rows(cin, cout, x_f32); }
 extern "C" int gdmae_spconv_stats(const void* X, int x_f32, const int* nbr, const void* packed, long long n, int cin, int cout, void* Y,

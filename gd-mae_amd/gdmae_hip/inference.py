@@ -1,0 +1,423 @@
+"""Inference engine of the fine-tuned CenterPoint detector (DynVFE -> SPTBackbone -> SSTBEVBackbone -> CenterHead).
+
+    engine = compile_detector(model)           # model: CenterPoint from build_network, .eval(), on the GPU
+    boxes, recall = engine(batch_dict)         # what model(batch_dict) returns in eval mode
+    maps = engine.head_maps(batch_dict)        # per-head prediction maps (+ .spatial_features_2d, ...)
+
+In evaluation mode every BatchNorm is a constant per-channel affine: a = gamma / sqrt(running_var + eps), b = beta - a running_mean.
+``compile_detector`` folds it into the weights of the product in front of it (W' = a W per output channel, computed in fp64 and
+rounded once to the operand type when the image is packed) and keeps b in fp32 for the product's epilogue, so that every
+product -> BatchNorm -> ReLU (-> + shortcut) block is ONE launch of libgdmae_hip.so and no framework convolution, BatchNorm, ReLU or
+GEMM kernel runs.  ``model.eval(); model(batch_dict)`` is not changed by any of this: it stays the exact (fp32) mode.
+
+The engine holds its own folded / packed copies.  It never writes to the model, runs under ``torch.no_grad()`` whatever the caller's
+grad mode, and refuses to run on stale images: the ``_version`` counters of every parameter and buffer are recorded at compile /
+``refresh()`` and compared at every call (optimizer steps of ``gdmae_hip.optim.FlatAdamOneCycle``, which updates its flat buffer
+without touching the counters, are seen through ``optim.GENERATION``).  Anything the kernels do not cover raises NotImplementedError.
+"""
+from __future__ import annotations
+
+import torch
+import torch.nn as nn
+
+from . import decoder as gdec
+from . import encoder as genc
+from . import lib as L
+from . import optim as goptim
+from . import packing
+from . import plan as gplan
+
+BF16 = torch.bfloat16
+
+
+def _pad32(c: int) -> int:
+    return (c + 31) // 32 * 32
+
+
+def _no(msg: str):
+    raise NotImplementedError("gdmae_hip.inference: " + msg)
+
+
+def fold_bn(bn, n_out: int, dev):
+    """(a, b) in fp64 of a BatchNorm in evaluation mode; bn = None: the identity."""
+    if bn is None:
+        return torch.ones(n_out, dtype=torch.float64, device=dev), torch.zeros(n_out, dtype=torch.float64, device=dev)
+    if isinstance(bn, nn.SyncBatchNorm):
+        _no("SyncBatchNorm (convert the model back with the statistics it holds)")
+    if not isinstance(bn, (nn.BatchNorm1d, nn.BatchNorm2d)):
+        _no(f"{type(bn).__name__} where a BatchNorm is expected")
+    if not bn.track_running_stats or bn.running_mean is None or bn.running_var is None:
+        _no("a BatchNorm without running statistics has no constant affine in evaluation mode")
+    if bn.num_features != n_out:
+        _no("BatchNorm width does not match the product in front of it")
+    var, mean = bn.running_var.detach().double(), bn.running_mean.detach().double()
+    gamma = bn.weight.detach().double() if bn.affine else torch.ones_like(var)
+    beta = bn.bias.detach().double() if bn.affine else torch.zeros_like(var)
+    a = gamma / torch.sqrt(var + float(bn.eps))
+    return a, beta - a * mean
+
+
+def _block(seq, kind):
+    """(product, BatchNorm) of a Sequential(product, BatchNorm, ReLU)."""
+    mods = list(seq.children())
+    if len(mods) != 3 or not isinstance(mods[0], kind) or not isinstance(mods[2], nn.ReLU):
+        _no(f"expected Sequential({kind.__name__}, BatchNorm, ReLU), got {[type(m).__name__ for m in mods]}")
+    return mods[0], mods[1]
+
+
+class _Dense:
+    """One Conv2d(3 x 3, stride 1, padding = dilation) launch: packed image of W' and the padded fp32 bias."""
+
+    def __init__(self, conv: nn.Conv2d, bn, relu: bool):
+        if not isinstance(conv, nn.Conv2d):
+            _no(f"{type(conv).__name__} where a Conv2d is expected")
+        d = int(conv.dilation[0])
+        cin, cout = conv.in_channels, conv.out_channels
+        if relu and cout % 32 != 0:
+            _no(f"dense block with {cout} output channels (the next convolution reads channels in multiples of 32)")
+        ok = (conv.kernel_size == (3, 3) and conv.stride == (1, 1) and conv.dilation == (d, d) and
+              conv.padding == (d, d) and d in (1, 2) and conv.groups == 1 and conv.padding_mode == 'zeros' and cin % 32 == 0 and
+              cin <= 1024 and cout <= 1024 and (d == 1 or (cin % 64 == 0 and cout % 64 == 0)))
+        if not ok:
+            _no(f"dense convolution {conv} (3 x 3, stride 1, padding = dilation in (1, 2), input channels in multiples of 32)")
+        dev = conv.weight.device
+        a, b = fold_bn(bn, cout, dev)
+        w = (conv.weight.detach().double() * a.view(-1, 1, 1, 1)).float().contiguous()
+        if conv.bias is not None:
+            b = b + a * conv.bias.detach().double()
+        self.cin, self.cout, self.cl, self.dil, self.relu = cin, cout, _pad32(cout), d, relu
+        self.packed = torch.empty(L.load().gdmae_conv3x3_dense_packed_bytes(cin, cout), dtype=torch.uint8, device=dev)
+        L.call("gdmae_conv3x3_dense_pack", L.ptr(w), cin, cout, d, 0, L.ptr(self.packed), L.stream())
+        self.bias = torch.zeros(self.cl, dtype=torch.float32, device=dev)
+        self.bias[:cout] = b.float()
+
+    def __call__(self, x, shortcut=None):
+        """x (B, H, W, cin) bf16 contiguous -> (B, H, W, pad32(cout)) bf16"""
+        B, H, W, c = x.shape
+        assert c == self.cin and x.dtype == BF16 and x.is_contiguous()
+        y = torch.empty(B, H, W, self.cl, dtype=BF16, device=x.device)
+        if self.relu:
+            L.call("gdmae_conv3x3_dense_relu", L.ptr(x), B, H, W, self.cin, self.cl, self.dil, L.ptr(self.packed), L.ptr(self.bias),
+                   None if shortcut is None else L.ptr(shortcut), L.ptr(y), L.stream())
+        else:
+            assert shortcut is None
+            L.call("gdmae_conv3x3_dense", L.ptr(x), B, H, W, self.cin, self.cl, self.dil, L.ptr(self.packed), L.ptr(self.bias), L.ptr(y),
+                   L.stream())
+        return y
+
+
+class _Sparse:
+    """One sparse convolution + folded BatchNorm + ReLU launch."""
+
+    def __init__(self, seq):
+        from pcdet.utils.spconv_utils import SparseConvolution
+        conv, bn = _block(seq, SparseConvolution)
+        cout, cin = conv.out_channels, conv.in_channels
+        if cin not in (128, 256) or cout not in (128, 256):
+            _no(f"sparse convolution {cin} -> {cout} (channels must be 128 or 256)")
+        a, b = fold_bn(bn, cout, conv.weight.device)
+        w = (conv.weight.detach().double() * a.view(-1, 1, 1, 1)).float().contiguous()       # (cout, 3, 3, cin)
+        self.packed, _ = packing.conv_pack_now(w)
+        self.bias = b.float().contiguous()
+        self.cin, self.cout, self.subm = cin, cout, conv.subm
+
+    def __call__(self, x, nbr):
+        n = nbr.shape[0]
+        y = torch.empty(n, self.cout, dtype=BF16, device=x.device)
+        if n:
+            L.call("gdmae_spconv_bias_relu", L.ptr(x), int(x.dtype == torch.float32), L.ptr(nbr), L.ptr(self.packed), L.ptr(self.bias), n,
+                   self.cin, self.cout, L.ptr(y), L.stream())
+        return y
+
+
+class _Stage:
+    """The encoder layers of one SSTBlockV1 through gdmae_encoder_stage_fwd (no autograd node): x -> x + layers(x) in bf16."""
+
+    def __init__(self, blk):
+        self.layers = [(layer, k) for block in blk.encoder_blocks for k, layer in enumerate(block.encoder_list)]
+        if not self.layers:
+            _no("an SST block without encoder layers")
+        self.bases, self.keep = [], []
+        for layer, _ in self.layers:
+            if layer.activation_name != "gelu":
+                _no("encoder activation other than gelu")
+            Win, bin_, tau, Wo, bo, W1, b1, W2, b2, g1, be1, g2, be2 = genc._plist(layer)
+            c16 = lambda t: t.detach().to(BF16).contiguous()                       # noqa: E731
+            f32 = lambda t: t.detach().float().clone().contiguous()                # noqa: E731
+            ts = {"Win": c16(Win), "bin": c16(bin_), "Wo": c16(Wo), "bo": c16(bo), "W1": c16(W1), "b1": c16(b1), "W2": c16(W2), "b2": c16(b2),
+                  "g1": f32(g1), "be1": f32(be1), "g2": f32(g2), "be2": f32(be2), "tau": f32(tau.reshape(1))}
+            packed = packing.pack_now(f32(Win), f32(Wo), f32(W1), f32(W2))
+            if packed is None:
+                _no("encoder weights must be fp32 device tensors")
+            ts["packed"] = packed
+            a = L.LayerArgs()
+            for k, t in ts.items():
+                setattr(a, k, L.ptr(t))
+            self.bases.append(a)
+            self.keep.append(ts)
+        l0 = self.layers[0][0]
+        sa = l0.win_attn.self_attn
+        self.nhead, self.tau_min, self.eps, self.ff = sa.num_heads, sa.tau_min, l0.norm1.eps, l0.linear1.weight.shape[0]
+        self.input_layer = blk.sst_input_layer
+
+    def __call__(self, x, wplans):
+        n, d = x.shape
+        dev = x.device
+        if n == 0:
+            return x.to(BF16)
+        nl = len(self.layers)
+        table = self.input_layer.pos_table(d, dev)
+        sb, fb, _ = genc._layer_bytes(n, d, self.ff, self.nhead, 1)
+        arr = (L.LayerArgs * nl)()
+        for i, (_, k) in enumerate(self.layers):
+            arr[i] = genc._call_args(self.bases[i], x, wplans[k % len(wplans)], table, self.nhead, self.tau_min, self.eps, BF16, self.ff)
+        # the forward entry also writes what only a backward reads (log-sum-exp rows, LayerNorm statistics, pre-GELU rows): `saved`
+        saved = torch.empty(nl, sb, dtype=torch.uint8, device=dev)
+        scratch = torch.empty(fb, dtype=torch.uint8, device=dev)
+        for i in range(nl):
+            arr[i].saved, arr[i].scratch = saved[i].data_ptr(), scratch.data_ptr()
+        fused = bool(L.load().gdmae_encoder_stage_fused(arr, nl))
+        folded = fused and x.dtype == BF16
+        res = torch.empty(n, d, dtype=BF16, device=dev)
+        if fused:
+            xin = x.contiguous() if folded else x.float().contiguous()
+            out = res if folded else torch.empty(n, d, dtype=torch.float32, device=dev)
+            for i in range(nl):
+                arr[i].x = xin.data_ptr() if i == 0 else 1 + i
+                arr[i].y = (2 + i) if i + 1 < nl else out.data_ptr()
+            if folded:
+                arr[0].x_bf16 = 1
+                arr[nl - 1].res_out = res.data_ptr()
+                arr[nl - 1].y = 0
+        else:
+            xin = x.float().contiguous()
+            ys = torch.empty(nl, n, d, dtype=torch.float32, device=dev)
+            for i in range(nl):
+                arr[i].x = (xin if i == 0 else ys[i - 1]).data_ptr()
+                arr[i].y = ys[i].data_ptr()
+            out = ys[nl - 1]
+        L.call("gdmae_encoder_stage_fwd", arr, nl, L.stream())
+        if not folded:
+            L.call("gdmae_add3_to", L.ptr(out), L.ptr(xin), 0, None, 0, out.numel(), L.ptr(res), 1, L.stream())
+        return res
+
+
+class HeadMaps(list):
+    """The per-head prediction dicts (what ``CenterHead.generate_predicted_boxes`` takes) plus the maps in front of them."""
+    spatial_features_2d = None
+    spatial_features = None
+    pillar_features = None
+    voxel_coords = None
+
+
+class DetectorEngine:
+    def __init__(self, model):
+        from pcdet.models.detectors.centerpoint import CenterPoint
+        from pcdet.models.backbones_3d.vfe.dyn_vfe import DynVFE
+        from pcdet.models.backbones_3d.spt_backbone import SPTBackbone
+        from pcdet.models.backbones_2d.sst_bev_backbone import SSTBEVBackbone
+        from pcdet.models.dense_heads.center_head import CenterHead
+        if not isinstance(model, CenterPoint):
+            _no(f"compile_detector covers the CenterPoint detector, not {type(model).__name__}")
+        if model.training:
+            raise ValueError("gdmae_hip.inference: compile_detector needs the model in evaluation mode (call model.eval() first)")
+        for name, kind in (("vfe", DynVFE), ("backbone_3d", SPTBackbone), ("backbone_2d", SSTBEVBackbone), ("dense_head", CenterHead)):
+            if not isinstance(getattr(model, name, None), kind):
+                _no(f"model.{name} must be a {kind.__name__}")
+        if getattr(model, "roi_head", None) is not None or getattr(model, "point_head", None) is not None:
+            _no("two-stage heads")
+        p0 = next(model.parameters())
+        if not p0.is_cuda:
+            _no("the model must be on the GPU")
+        self.model = model
+        self.refresh()
+
+    # ---- freshness -------------------------------------------------------------------------------------------------
+    def _stamp(self):
+        """What a call compares with compile / refresh() time: identity, version counter and storage address of every parameter and
+        buffer the model holds NOW (a tensor replaced by assignment, an in-place update, a .to() / load that moved storage), and the
+        count of FlatAdamOneCycle steps in this process.  Known gaps: a write through ``.data`` of the same storage bumps no counter
+        and is not seen; the step count is process-wide, so a flat-optimizer step on ANY model makes every engine stale (it errs on
+        the side of a refresh)."""
+        ts = list(self.model.parameters()) + list(self.model.buffers())
+        return (tuple((id(t), t._version, t.data_ptr()) for t in ts), goptim.GENERATION)
+
+    def _check_fresh(self):
+        if self.model.training:
+            raise RuntimeError("gdmae_hip.inference: the model is in training mode; the engine serves model.eval()")
+        if self._stamp() != self._stamped:
+            raise RuntimeError("gdmae_hip.inference: the model's parameters or buffers changed since compile_detector / refresh(); "
+                               "call engine.refresh() to rebuild the folded weight images")
+
+    @torch.no_grad()
+    def refresh(self):
+        """(Re)build every folded, packed weight image from the model's current parameters and BatchNorm buffers."""
+        m = self.model
+        stamp = self._stamp()
+        dev = next(m.parameters()).device
+        # DynVFE: Linear (no bias) -> BatchNorm1d -> ReLU, twice
+        mlp = m.vfe.dvfe_mlps[0]
+        if len(mlp) != 6 or not isinstance(mlp[0], nn.Linear) or not isinstance(mlp[3], nn.Linear):
+            _no("DynVFE with other than two Linear-BatchNorm-ReLU layers")
+        l1, bn1, l2, bn2 = mlp[0], mlp[1], mlp[3], mlp[4]
+        if l1.out_features != 64 or l2.in_features != 64 or l2.out_features != 128:
+            _no(f"DynVFE layers {l1.out_features}, {l2.out_features} (the kernel takes 64 and 128)")
+        vw = []
+        for lin, bn in ((l1, bn1), (l2, bn2)):
+            a, b = fold_bn(bn, lin.out_features, dev)
+            w = (lin.weight.detach().double() * a.view(-1, 1)).float().contiguous()
+            if lin.bias is not None:
+                b = b + a * lin.bias.detach().double()
+            vw += [w, b.float().contiguous()]
+        self.vfe_w = vw
+        # encoder stages + the five sparse convolutions
+        bb = m.backbone_3d
+        self.stages = []
+        for blk in bb.sst_blocks:
+            self.stages.append((None if blk.conv_down is None else _Sparse(blk.conv_down), _Stage(blk), _Sparse(blk.conv_out)))
+        # decoder: ConvTranspose2d(k = s) rows per source stage, one constant background row, conv_out
+        self.deblocks = []
+        bg = []
+        for blk in bb.deblocks:
+            dc, bn = _block(blk, nn.ConvTranspose2d)
+            s = int(dc.stride[0])
+            cin, cout = dc.in_channels, dc.out_channels
+            if not (dc.kernel_size == (s, s) and dc.stride == (s, s) and dc.bias is None and dc.padding == (0, 0) and dc.output_padding == (0, 0)
+                    and cin in (128, 256) and cout == 128 and s in (1, 2, 4) and dc.groups == 1):
+                _no(f"decoder deblock {dc}")
+            a, b = fold_bn(bn, cout, dev)
+            w = (dc.weight.detach().double() * a.view(1, -1, 1, 1)).float().contiguous()
+            nb = L.load().gdmae_deconv_rows_packed_bytes(cin, cout, s)
+            pf = torch.empty(nb, dtype=torch.uint8, device=dev)
+            pb = torch.empty(nb, dtype=torch.uint8, device=dev)
+            L.call("gdmae_deconv_rows_pack", L.ptr(w), cin, cout, s, L.ptr(pf), L.ptr(pb), L.stream())
+            self.deblocks.append((pf, b.float().contiguous(), cin, cout, s))
+            bg.append(torch.clamp_min(b, 0.0))
+        self.dec_bg = torch.cat(bg).float().to(BF16).contiguous()           # an empty site of branch i holds relu(b_i), not zero
+        self.dec_ones = torch.ones(128, dtype=torch.float32, device=dev)
+        self.dec_sources = [int(src[-1]) - 1 for src in bb.model_cfg.FEATURES_SOURCE]
+        conv, bn = _block(bb.conv_out, nn.Conv2d)
+        self.dec_out = _Dense(conv, bn, True)
+        if self.dec_out.cin != self.dec_bg.numel():
+            _no("decoder conv_out width")
+        # BEV backbone
+        self.bev = []
+        c = self.dec_out.cout
+        for i, blk in enumerate(m.backbone_2d.conv_layer):
+            conv, bn = _block(blk, nn.Conv2d)
+            if conv.in_channels != c:
+                _no("BEV block input width does not follow the block before it")
+            self.bev.append((_Dense(conv, bn, True), conv.out_channels == c and i in m.backbone_2d.conv_shortcut))
+            c = conv.out_channels
+        # head
+        hd = m.dense_head
+        conv, bn = _block(hd.shared_conv, nn.Conv2d)
+        self.shared = _Dense(conv, bn, True)
+        if self.shared.cin != c:
+            _no("shared_conv input width does not follow the BEV backbone")
+        self.heads = []
+        for head in hd.heads_list:
+            branches = []
+            for name in head.sep_head_dict:
+                seq = list(getattr(head, name).children())
+                ops, w = [], self.shared.cout
+                for layer in seq[:-1]:
+                    conv, bn = _block(layer, nn.Conv2d)
+                    ops.append(_Dense(conv, bn, True))
+                    if ops[-1].cin != w:
+                        _no(f"head branch {name}: channel widths do not chain")
+                    w = ops[-1].cout
+                if not isinstance(seq[-1], nn.Conv2d):
+                    _no("head branch must end in a Conv2d")
+                ops.append(_Dense(seq[-1], None, False))
+                if ops[-1].cin != w:
+                    _no(f"head branch {name}: channel widths do not chain")
+                branches.append((name, ops))
+            self.heads.append(branches)
+        self._stamped = stamp
+        return self
+
+    # ---- one forward -----------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def head_maps(self, batch_dict) -> HeadMaps:
+        self._check_fresh()
+        from pcdet.models.backbones_3d.spt_backbone import stage_plan_args
+        m = self.model
+        vfe, bb = m.vfe, m.backbone_3d
+        B = int(batch_dict['batch_size'])
+        vox = batch_dict.get('_gdmae_vox', None)
+        if vox is None:
+            vox = gplan.voxelize(batch_dict['points'], vfe.point_cloud_range, vfe.voxel_size, vfe.grid_size, B)
+        if not 3 <= vox.n_cols - 1 <= 5 or vox.points_pm is None:
+            _no("points with 3 to 5 features in pillar-major order")
+        dev = vox.voxel_coords.device
+        with torch.autocast("cuda", enabled=False):
+            pf = torch.empty(vox.M, 128, dtype=torch.float32, device=dev)
+            w1, b1, w2, b2 = self.vfe_w
+            L.call("gdmae_vfe_infer", L.ptr(vox.points_pm), L.ptr(vox.voxel_coords), L.ptr(vox.row_pillar), L.ptr(vox.pillar_mean), int(vox.N),
+                   int(vox.M), vox.n_cols, L.host_f32(vox.lo), L.host_f32(vox.vs), L.ptr(w1), L.ptr(b1), 64, L.ptr(w2), L.ptr(b2), 128, L.ptr(pf),
+                   L.stream())
+            ep = gplan.encoder_plan(vox, *stage_plan_args(bb.model_cfg.SST_BLOCK_LIST), keep_frac=None)
+            x, si, hidden = pf, 0, []
+            for down, stage, conv_out in self.stages:
+                if down is not None:
+                    si += 1
+                    x = down(x, ep.stages[si].nbr_down)
+                sp = ep.stages[si]
+                x = conv_out(stage(x, sp.windows), sp.nbr_subm)
+                hidden.append((x, sp))
+            # decoder: the concatenated map = the constant row everywhere + relu(P' + b_i) at the sites the tokens cover
+            srcs = [hidden[i] for i in self.dec_sources]
+            s0 = self.deblocks[0][4]
+            Y, X = srcs[0][1].Y * s0, srcs[0][1].X * s0
+            ctot = self.dec_bg.numel()
+            Z = torch.empty(B * Y * X, ctot, dtype=BF16, device=dev)
+            L.call("gdmae_fill_rows", L.ptr(self.dec_bg), B * Y * X, ctot, 2, L.ptr(Z), L.stream())
+            col0 = 0
+            for (pf_img, b, cin, cout, s), (h, sp) in zip(self.deblocks, srcs):
+                if sp.Y * s != Y or sp.X * s != X or sp.B != B:
+                    _no("decoder sources of different full-resolution sizes")
+                n = h.shape[0]
+                if n:
+                    P = torch.empty(n * s * s, cout, dtype=BF16, device=dev)
+                    L.call("gdmae_deconv_rows_fwd", L.ptr(h), n, cin, cout, s, L.ptr(pf_img), L.ptr(P), L.stream())
+                    sites = gdec.upsampled_sites(sp, s, Y, X).contiguous()
+                    L.call("gdmae_rows_affine_relu_scatter", L.ptr(P), 1, L.ptr(sites), n * s * s, cout, L.ptr(self.dec_ones), L.ptr(b), L.ptr(Z), 1,
+                           ctot, col0, L.stream())
+                col0 += cout
+            sf = self.dec_out(Z.view(B, Y, X, ctot))
+            x2 = sf
+            for conv, shortcut in self.bev:
+                x2 = conv(x2, x2 if shortcut else None)
+            xs = self.shared(x2)
+            out = HeadMaps()
+            for branches in self.heads:
+                pd = {}
+                for name, ops in branches:
+                    y = xs
+                    for op in ops:
+                        y = op(y)
+                    pd[name] = y[..., :ops[-1].cout].permute(0, 3, 1, 2)
+                out.append(pd)
+        out.spatial_features_2d = x2.permute(0, 3, 1, 2)
+        out.spatial_features = sf.permute(0, 3, 1, 2)
+        out.pillar_features = pf
+        out.voxel_coords = vox.voxel_coords
+        return out
+
+    @torch.no_grad()
+    def __call__(self, batch_dict):
+        maps = self.head_maps(batch_dict)
+        B = int(batch_dict['batch_size'])
+        m = self.model
+        with torch.autocast("cuda", enabled=False):
+            boxes = m.dense_head.generate_predicted_boxes(B, maps)
+            bd = {'final_box_dicts': boxes, 'batch_size': B}
+            if 'gt_boxes' in batch_dict:
+                bd['gt_boxes'] = batch_dict['gt_boxes']
+            return m.post_processing(bd)
+
+
+def compile_detector(model) -> DetectorEngine:
+    """Fold and pack ``model`` (a CenterPoint from ``pcdet.models.build_network``, in eval mode, on the GPU) for inference."""
+    return DetectorEngine(model)

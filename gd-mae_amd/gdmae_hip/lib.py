@@ -30,6 +30,7 @@ SIGNATURES = {
     "gdmae_voxelize_workspace_bytes": (_Z, [_L, _I, _I, _I, _I]),
     "gdmae_voxelize": (_I, [_P, _L, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
     "gdmae_decorate_points": (_I, [_P, _P, _P, _P, _L, _I, _P, _P, _P, _P]),
+    "gdmae_vfe_infer": (_I, [_P, _P, _P, _P, _L, _L, _I, _P, _P, _P, _P, _I, _P, _P, _I, _P, _P]),
     "gdmae_vfe_point_layer_workspace_bytes": (_Z, [_I]),
     "gdmae_pillar_major_rows": (_I, [_P, _I, _P, _P, _P, _L, _P, _P, _P]),
     "gdmae_vfe_point_layer_fwd": (_I, [_P, _P, _P, _P, _I, _L, _I, _P, _P, _P, _I, _P, _P, _D, _D, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P]),
@@ -92,6 +93,7 @@ SIGNATURES = {
     "gdmae_conv3x3_dense_pack": (_I, [_P, _I, _I, _I, _I, _P, _P]),
     "gdmae_conv3x3_dense": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "gdmae_conv3x3_dense_add": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "gdmae_conv3x3_dense_relu": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "gdmae_conv3x3_dense_stats_workspace_bytes": (_Z, [_I, _I, _I, _I]),
     "gdmae_conv3x3_dense_stat_rows": (_I, []),
     "gdmae_conv3x3_dense_stats": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
@@ -126,6 +128,7 @@ SIGNATURES = {
     "gdmae_spconv_packed_bytes": (_Z, [_I, _I]),
     "gdmae_spconv_pack_jobs": (_I, [_P, _I, _I, _I, _P, _P]),
     "gdmae_spconv": (_I, [_P, _I, _P, _P, _L, _I, _I, _P, _I, _P]),
+    "gdmae_spconv_bias_relu": (_I, [_P, _I, _P, _P, _P, _L, _I, _I, _P, _P]),
     "gdmae_spconv_stat_rows": (_I, [_I, _I, _I]),
     "gdmae_spconv_stats": (_I, [_P, _I, _P, _P, _L, _I, _I, _P, _P, _P]),
     "gdmae_decoder_dy": (_I, [_P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _P, _P]),

@@ -19,6 +19,9 @@ import torch.distributed as dist
 
 from . import lib as L
 
+# bumped by every FlatAdamOneCycle.step(): consumers that hold images of parameter VALUES (gdmae_hip.inference) compare it
+GENERATION = 0
+
 
 def one_cycle(step: int, total_step: int, lr_max: float, moms, div_factor: float, pct_start: float):
     """(lr, beta1) of the reference OneCycle at ``step`` (cosine anneal, two phases, later phase wins)."""
@@ -212,6 +215,8 @@ class FlatAdamOneCycle:
             dist.broadcast(b, src=src, group=self.pg)
 
     def step(self, accumulated_iter: int | None = None):
+        global GENERATION
+        GENERATION += 1       # the update below changes parameter values without touching their _version counters
         self._check_views()
         it = self.t if accumulated_iter is None else accumulated_iter
         c = self.cfg

@@ -82,6 +82,15 @@ int gdmae_decorate_points(const float* points, const long long* point_coords, co
  * (device-side count, e.g. gdmae_voxelize counts[0]; buffers sized for `capacity` rows). */
 int gdmae_pillar_major_rows(const float* points, int n_cols, const int* pillar_pts, const int* inverse32, const int* n_dev,
                             long long capacity, float* points_pm, int* row_pillar, void* stream);
+/* Both DynVFE layers and the pillar maximum for INFERENCE in one kernel (csrc/vfe_infer.hip): out (M, 128) fp32 =
+ * max over the pillar's points of relu(W2 relu(W1 f + b1) + b2), f = the decorated features of gdmae_decorate_points computed on the fly
+ * from the pillar-major rows (points_pm, row_pillar of gdmae_pillar_major_rows; voxel_coords (M, 4) int64; pillar_mean (M, F)).
+ * W1 (64, 6 + F) / b1 (64) / W2 (128, 64) / b2 (128) fp32: the Linear weights with the BatchNorm1d running-statistics affine folded in
+ * by the caller.  Layer 1 multiplies in fp32, layer 2 with fp16 operands (W2 rounded in the kernel) and fp32 accumulation.  Nothing of
+ * size N is written.  `out` is cleared by the call; N = 0 or M = 0 returns without a launch. */
+int gdmae_vfe_infer(const float* points_pm, const long long* voxel_coords, const int* row_pillar, const float* pillar_mean,
+                    long long N, long long M, int n_cols, const float* lo, const float* vs, const float* W1, const float* b1,
+                    int c1, const float* W2, const float* b2, int c2, float* out, void* stream);
 size_t gdmae_vfe_point_layer_workspace_bytes(int n_cols);
 int gdmae_vfe_point_layer_fwd(const float* points, const long long* point_coords, const int* inverse32,
                               const float* pillar_mean, int coords_per_pillar, long long N, int n_cols, const float* lo,
@@ -487,6 +496,10 @@ size_t gdmae_spconv_packed_bytes(int cin, int cout);
 int gdmae_spconv_pack_jobs(const float* W /* (cout, 3, 3, cin) fp32 */, int cin, int cout, int transposed, void* packed, long long* jobs);
 int gdmae_spconv(const void* X, int x_f32, const int* nbr, const void* packed, long long n, int cin, int cout, void* Y,
                  int timing_slot /* 0: the sparse-conv forward slot of gdmae_kernel_timing */, void* stream);
+/* The same launch with the epilogue Y = relu(acc + bias), bias (cout) fp32: a conv block (SubMConv2d / SparseConv2d -> BatchNorm1d ->
+ * ReLU) in evaluation mode, the running-statistics affine folded into the packed images and the bias by the caller. */
+int gdmae_spconv_bias_relu(const void* X, int x_f32, const int* nbr, const void* packed, const float* bias, long long n, int cin, int cout,
+                           void* Y, void* stream);
 /* The same launch with the BatchNorm statistics of Y as its epilogue: part (ceil(n / gdmae_spconv_stat_rows(cin, cout, x_f32)), 2, cout)
  * fp32 = per-workgroup column sums of Y and Y^2 (of the bf16-rounded values), to be folded by gdmae_bn_fold_partials - what
  * gdmae_conv_block_fwd does instead of a statistics pass over Y (post_act_block's BatchNorm1d, spconv_utils.py:37-56). */
@@ -675,6 +688,11 @@ int gdmae_conv3x3_dense(const void* X, int B, int H, int W, int cin_l, int cout_
  * block's input joins the convolution's input gradient (sst_bev_backbone.py:36-40) */
 int gdmae_conv3x3_dense_add(const void* X, int B, int H, int W, int cin_l, int cout_l, int dil, const void* packed, const float* bias,
                             const void* addend, void* Y, void* stream);
+/* Y = relu(conv(X) + bias), rounded to bf16, then + shortcut (B, H, W, cout_l) bf16 when not NULL (ReLU first, then the add, as
+ * gdmae_hip.dense.conv_bn_relu orders them): a Conv2d -> BatchNorm2d -> ReLU block in evaluation mode as ONE launch, the
+ * running-statistics affine folded into the packed weights and the bias by the caller */
+int gdmae_conv3x3_dense_relu(const void* X, int B, int H, int W, int cin_l, int cout_l, int dil, const void* packed, const float* bias,
+                             const void* shortcut, void* Y, void* stream);
 /* ... + the statistics of the BatchNorm that follows the convolution as its epilogue: stat_rows (gdmae_conv3x3_dense_stat_rows() = 256,
  * 2, cout_l) fp32 partial rows {sum, sum of squares} per channel of the ROUNDED outputs over all B H W sites, summed in a fixed order;
  * gdmae_bn_fold_partials turns them into the folded affine (no pass over Y).  workspace: gdmae_conv3x3_dense_stats_workspace_bytes. */
