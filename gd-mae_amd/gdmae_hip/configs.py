@@ -90,6 +90,35 @@ def center_head_iou_cfg(class_names=('Vehicle', 'Pedestrian', 'Cyclist'), post_r
     return c
 
 
+def anchor_head_cfg():
+    """DENSE_HEAD section of tools/cfgs/kitti_models/gd_mae.yaml:191-247 (AnchorHeadSingle)."""
+    def a(name, size, z, mt, ut):
+        return {'class_name': name, 'anchor_sizes': [size], 'anchor_rotations': [0, 1.57], 'anchor_bottom_heights': [z],
+                'align_center': False, 'feature_map_stride': 1, 'matched_threshold': mt, 'unmatched_threshold': ut}
+    return AttrDict({
+        'NAME': 'AnchorHeadSingle', 'CLASS_AGNOSTIC': False, 'USE_DIRECTION_CLASSIFIER': True, 'DIR_OFFSET': 0.78539,
+        'DIR_LIMIT_OFFSET': 0.0, 'NUM_DIR_BINS': 2,
+        'ANCHOR_GENERATOR_CONFIG': [a('Car', [3.9, 1.6, 1.56], -1.78, 0.6, 0.45), a('Pedestrian', [0.8, 0.6, 1.73], -0.6, 0.5, 0.35),
+                                    a('Cyclist', [1.76, 0.6, 1.73], -0.6, 0.5, 0.35)],
+        'TARGET_ASSIGNER_CONFIG': {'NAME': 'AxisAlignedTargetAssigner', 'POS_FRACTION': -1.0, 'SAMPLE_SIZE': 512,
+                                   'NORM_BY_NUM_EXAMPLES': False, 'MATCH_HEIGHT': False, 'BOX_CODER': 'ResidualCoder'},
+        'LOSS_CONFIG': {'LOSS_WEIGHTS': {'cls_weight': 1.0, 'loc_weight': 2.0, 'dir_weight': 0.2, 'code_weights': [1.0] * 7}},
+    })
+
+
+def kitti_finetune_cfg():
+    """MODEL section of the shipped KITTI fine-tune config (tools/cfgs/kitti_models/gd_mae.yaml:54-260): PointPillar detector =
+    DynVFE -> SPTBackbone -> SSTBEVBackbone -> AnchorHeadSingle at 0.32 m pillars (216 x 248).  -> (model_cfg, dataset_info)."""
+    ssl = gdmae_ssl_model_cfg(0.0, eval_metric='kitti')
+    m = AttrDict({'NAME': 'PointPillar', 'VFE': ssl.VFE, 'BACKBONE_3D': gdmae_finetune_backbone_cfg(), 'BACKBONE_2D': sst_bev_backbone_cfg(),
+                  'DENSE_HEAD': anchor_head_cfg(),
+                  'POST_PROCESSING': {'RECALL_THRESH_LIST': [0.3, 0.5, 0.7], 'SCORE_THRESH': 0.3, 'OUTPUT_RAW_SCORE': False,
+                                      'EVAL_METRIC': 'kitti',
+                                      'NMS_CONFIG': {'MULTI_CLASSES_NMS': False, 'NMS_TYPE': 'nms_gpu', 'NMS_THRESH': 0.01,
+                                                     'NMS_PRE_MAXSIZE': 4096, 'NMS_POST_MAXSIZE': 500}}})
+    return m, SyntheticDatasetInfo(**KITTI)
+
+
 def optimization_cfg(batch_size_per_gpu=8, num_epochs=30):
     """OPTIMIZATION section of the ssl yamls (gd_mae_ssl.yaml:183-203)."""
     return AttrDict({'BATCH_SIZE_PER_GPU': batch_size_per_gpu, 'NUM_EPOCHS': num_epochs, 'OPTIMIZER': 'adam_onecycle',

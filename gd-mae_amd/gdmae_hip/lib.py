@@ -181,6 +181,13 @@ SIGNATURES = {
     "gdmae_focal_loss_fwd": (_I, [_P, _I, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
     "gdmae_focal_loss_bwd": (_I, [_P, _I, _P, _P, _I, _I, _I, _I, _P, _P, _P, _I, _P]),
     "gdmae_center_head_decode": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _F, _P, _F, _I, _P, _P, _P, _P, _P]),
+    "gdmae_anchor_targets_workspace_bytes": (_Z, [_I, _I, _I]),
+    "gdmae_anchor_targets": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _F, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "gdmae_anchor_loss_rows": (_I, []),
+    "gdmae_anchor_loss_fwd": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "gdmae_anchor_loss_bwd": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "gdmae_anchor_decode": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _F, _F, _P, _P, _P]),
+    "gdmae_anchor_select": (_I, [_P, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P]),
     "gdmae_boxes_bev_pairs": (_I, [_P, _I, _P, _I, _I, _P, _P]),
     "gdmae_nms_workspace_bytes": (_Z, [_I]),
     "gdmae_nms_bev": (_I, [_P, _I, _F, _I, _P, _P, _P, _P]),

@@ -1,11 +1,13 @@
 from .detector3d_template import Detector3DTemplate
 from .centerpoint import CenterPoint
 from .gd_mae import GDMAE
+from .pointpillar import PointPillar
 
 __all__ = {
     'Detector3DTemplate': Detector3DTemplate,
     'GDMAE': GDMAE,
     'CenterPoint': CenterPoint,
+    'PointPillar': PointPillar,
 }
 
 

@@ -118,6 +118,72 @@ class Detector3DTemplate(nn.Module):
             recall_dict['gt_num'] += gt.shape[0]
         return recall_dict
 
+    def post_processing(self, batch_dict):
+        """(pred_dicts, recall_dict) from ``batch_cls_preds`` (B, n, n_class) / ``batch_box_preds`` (B, n, 7) tensors: the shipped
+        branch of the reference's post_processing (detector3d_template.py:196-316) - sigmoid unless ``cls_preds_normalized``, best
+        class -> label + 1, ``class_agnostic_nms`` (model_nms_utils.py:6-25: SCORE_THRESH mask, the NMS_PRE_MAXSIZE best, rotated
+        NMS, NMS_POST_MAXSIZE) and the recall record.  On the device the scores never reach torch ops: ``gdmae_anchor_select`` (one
+        launch for the whole batch) leaves the anchors above the threshold compacted in anchor order, so the top-k, the gather
+        and the NMS see a few hundred rows per sample instead of n.  ``fused_select = False``: the same with torch ops."""
+        cfg = self.model_cfg.POST_PROCESSING
+        nms = cfg.NMS_CONFIG
+        if nms.MULTI_CLASSES_NMS:
+            raise NotImplementedError("MULTI_CLASSES_NMS: True (per-class NMS in post_processing) is not built")
+        if isinstance(batch_dict['batch_cls_preds'], list) or isinstance(batch_dict['batch_box_preds'], list):
+            raise NotImplementedError("list-valued batch_cls_preds / batch_box_preds (multi-head) are not built")
+        if batch_dict.get('has_class_labels', False):
+            raise NotImplementedError("has_class_labels (labels from a RoI head) is not built in post_processing")
+        if batch_dict.get('batch_index', None) is not None:
+            raise NotImplementedError("batch_index (concatenated predictions) is not built in post_processing")
+        if not nms.get('NMS', True) or cfg.get('OUTPUT_RAW_SCORE', False) or nms.NMS_TYPE != 'nms_gpu':
+            raise NotImplementedError("post_processing: only NMS_TYPE nms_gpu with OUTPUT_RAW_SCORE False is built")
+        from ...ops.iou3d_nms import iou3d_nms_utils
+        from gdmae_hip import lib as L
+        cls_all, box_all = batch_dict['batch_cls_preds'], batch_dict['batch_box_preds']
+        B = batch_dict['batch_size']
+        assert box_all.dim() == 3 and cls_all.shape[2] in (1, self.num_class)
+        normalized = bool(batch_dict['cls_preds_normalized'])
+        thresh = cfg.SCORE_THRESH
+        fused = getattr(self, 'fused_select', True) and cls_all.is_cuda and thresh is not None
+        if fused:
+            n, C = cls_all.shape[1], cls_all.shape[2]
+            cls_c = cls_all.float().contiguous()
+            idx = torch.empty(B, n, dtype=torch.int32, device=cls_c.device)
+            score = torch.empty(B, n, dtype=torch.float32, device=cls_c.device)
+            label = torch.empty(B, n, dtype=torch.int32, device=cls_c.device)
+            count = torch.empty(B, dtype=torch.int32, device=cls_c.device)
+            L.call("gdmae_anchor_select", L.ptr(cls_c), B, n, C, int(normalized), float(thresh), L.ptr(idx), L.ptr(score), L.ptr(label),
+                   L.ptr(count), L.stream())
+            counts = count.tolist()                     # the one host read of the call: the output shapes depend on it
+        recall_dict, pred_dicts = {}, []
+        for b in range(B):
+            box_preds = box_all[b]
+            if fused:
+                m = counts[b]
+                orig, scores, labels = idx[b, :m].long(), score[b, :m], label[b, :m].long()
+            else:
+                cp = cls_all[b] if normalized else torch.sigmoid(cls_all[b])
+                sc_all, lab_all = torch.max(cp, dim=-1)
+                lab_all = lab_all + 1
+                mask = sc_all >= thresh if thresh is not None else torch.ones_like(sc_all, dtype=torch.bool)
+                orig = mask.nonzero().view(-1)
+                scores, labels = sc_all[orig], lab_all[orig]
+            if scores.shape[0] > 0:
+                top_scores, top = torch.topk(scores, k=min(int(nms.NMS_PRE_MAXSIZE), scores.shape[0]))
+                keep, _ = iou3d_nms_utils.nms_gpu(box_preds[orig[top]][:, 0:7], top_scores, nms.NMS_THRESH)
+                sel = top[keep[:int(nms.NMS_POST_MAXSIZE)]]
+            else:
+                sel = torch.zeros(0, dtype=torch.int64, device=scores.device)
+            final_scores, final_labels, final_boxes = scores[sel], labels[sel], box_preds[orig[sel]]
+            ok = final_labels != 0
+            final_boxes, final_scores, final_labels = final_boxes[ok], final_scores[ok], final_labels[ok]
+            if cfg.get('RECALL_MODE', 'normal') == 'normal':
+                recall_dict = self.generate_recall_record(box_preds=final_boxes if 'rois' not in batch_dict else box_preds,
+                                                          recall_dict=recall_dict, batch_index=b, data_dict=batch_dict,
+                                                          thresh_list=cfg.RECALL_THRESH_LIST)
+            pred_dicts.append({'pred_boxes': final_boxes, 'pred_scores': final_scores, 'pred_labels': final_labels})
+        return pred_dicts, recall_dict
+
     def forward(self, **kwargs):
         raise NotImplementedError
 

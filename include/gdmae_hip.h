@@ -850,6 +850,36 @@ size_t gdmae_nms_workspace_bytes(int n);
 int gdmae_nms_bev(const float* boxes, int n, float thresh, int rotated, long long* keep, int* n_keep, void* workspace,
                   void* stream);
 
+/* ---- anchor head of the KITTI fine-tune config (csrc/anchor_head.hip; reference anchor_head_template.py:88-266,
+ * axis_aligned_target_assigner.py:36-210) ------------------------------------------------------- *
+ * Anchor index a = (y W + x) K + k (k: anchor slot of a location, class-major then size then rotation), A = H W K.  Device
+ * tables filled from the generated anchors: slot_cls (K) int anchor class of a slot, xr (K, W, 2) / yr (K, H, 2) edges of the
+ * anchors' nearest axis-aligned rectangles, xc (W) / yc (H) centres, slot (K, 5) z, dx, dy, dz, rotation.
+ * anchor_targets: three launches for all samples and classes; gt_boxes (B, n_max <= 512, box_dim) fp32 with the class last;
+ *   name_idx / matched / unmatched: HOST arrays (n_cls <= 8).  Outputs fully written: labels (-1 ignored, 0 background, class),
+ *   gt_ids (row of gt_boxes[b] or -1), dir_bins (-1 where nothing is regressed) (B, A) int32, reg_targets (B, A, 7), num_pos (B).
+ * anchor_loss: rows (B n_loc, ld) head output [cls K C | box K 7 | dir K nb | padding], bf16 or fp32; scale = LOSS_WEIGHTS / B
+ *   (HOST, 3), code_weights HOST (7); out4 = {cls, loc, dir, sum}; bwd writes every element of drows (rows' type).
+ * anchor_decode: cls_out (B, A, C) logits, boxes (B, A, 7) decoded with the direction-bin correction.
+ * anchor_select: per sample the anchors whose best-class sigmoid score >= thresh, compacted in anchor order. */
+size_t gdmae_anchor_targets_workspace_bytes(int B, int n_cls, int n_max);
+int gdmae_anchor_targets(const float* gt_boxes, int B, int n_max, int box_dim, int H, int W, int K, int n_cls, int n_names,
+                         const int* name_idx, const int* slot_cls, const float* xr, const float* yr, const float* xc, const float* yc,
+                         const float* slot, const float* matched, const float* unmatched, float dir_offset, int num_bins,
+                         int* labels, int* gt_ids, float* reg_targets, int* dir_bins, int* num_pos, void* workspace, void* stream);
+int gdmae_anchor_loss_rows(void);
+int gdmae_anchor_loss_fwd(const void* rows, int rows_bf16, int ld, int B, int n_loc, int K, int C, int nb, const int* labels,
+                          const float* reg_targets, const int* dir_bins, const int* num_pos, const float* code_weights,
+                          const float* scale, float* partials, float* out4, void* stream);
+int gdmae_anchor_loss_bwd(const void* rows, int rows_bf16, int ld, int B, int n_loc, int K, int C, int nb, const int* labels,
+                          const float* reg_targets, const int* dir_bins, const int* num_pos, const float* code_weights,
+                          const float* scale, const float* grad3, void* drows, void* stream);
+int gdmae_anchor_decode(const void* rows, int rows_bf16, int ld, int B, int H, int W, int K, int C, int nb, const float* xc,
+                        const float* yc, const float* slot, float dir_offset, float dir_limit_offset, float* cls_out, float* boxes,
+                        void* stream);
+int gdmae_anchor_select(const float* cls, int B, int n, int C, int normalized, float thresh, int* idx, float* score, int* label,
+                        int* count, void* stream);
+
 /* ---- a21: fused optimizer step over one flat buffer ------------------------------------------- *
  * Replaces clip_grad_norm_ (tools/train_utils/train_utils.py:52) and OptimWrapper.step
  * (tools/train_utils/optimization/fastai_optim.py:135-152: p *= 1 - wd*lr, then torch Adam). */
