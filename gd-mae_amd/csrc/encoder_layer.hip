@@ -1,14 +1,23 @@
 // Native executor of one post-norm encoder layer: the whole forward or backward of
 // EncoderLayer.forward (reference pcdet/models/model_utils/sst_basic_block.py:77-84, WindowAttention :22-54,
-// cosine attention cosine_msa.py) is ONE C-ABI call that enqueues ~17 (forward) / ~40 (backward) kernels on the
-// caller's stream: token-wise GEMMs through hipBLASLt (algorithms cached per problem shape), everything else the
-// hand-written kernels of this library.  At 20-40 k tokens per stage each kernel runs for 5-40 us, so the layer is
-// bound by how fast the host can enqueue: issuing it from an interpreter (one framework op per kernel) costs
-// ~1.1 ms of host time per layer and direction against ~0.8 ms of GPU work; from here it costs tens of microseconds.
+// cosine attention cosine_msa.py) is ONE C-ABI call that enqueues its kernels on the caller's stream.  At 20-40 k
+// tokens per stage each kernel runs for 5-40 us, so the layer is bound by how fast the host can enqueue: issuing it
+// from an interpreter (one framework op per kernel) costs ~1.1 ms of host time per layer and direction against
+// ~0.8 ms of GPU work; from here it costs tens of microseconds.
 //
-// Rows are padded to a multiple of 2048 (pad rows are zero or finite and never read as results) so that
-//  * the GEMM shapes repeat from step to step (token counts differ per batch; hipBLASLt heuristics are cached), and
-//  * every weight gradient g^T x is ONE batched split-K GEMM over equal K chunks + one reduce-accumulate kernel.
+// A layer runs ONE of three schedules (layer_schedule), each written out top to bottom below:
+//  LIBRARY      fp32 rows, or bf16 rows without a packed weight image / with other widths: gd_gemm products (gemm.h),
+//               separate GELU / LayerNorm / column-sum kernels, one batched split-K GEMM + reduce per weight gradient,
+//               gdmae_add3                                                                     (layer_lib_fwd / layer_lib_bwd)
+//  PER_PRODUCT  bf16 rows, packed image, d in {128, 256}, ff = 2 d, args.path = 0: one k_tok_gemm launch per product with
+//               row epilogues, k_tok_ffn, LayerNorm backward as GEMM epilogue, one grouped weight-gradient launch +
+//               k_layer_tail, fp32 residual stream                                            (layer_tok_fwd / layer_tok_bwd)
+//  FUSED        the same layers as a stage call with args.path = 1 (the product): three launches per layer and direction
+//               around the attention, bf16 residual stream (layer_fused.hip)                      (stage_fwd_v2 / stage_bwd_v2)
+//
+// Rows are padded to a multiple of 2048 so that the GEMM shapes repeat from step to step (token counts differ per batch)
+// and every weight gradient g^T x splits into equal K chunks.  LIBRARY zeroes the pad rows of every GEMM operand; the
+// hand-written kernels of the other two ignore rows >= n (pad rows are finite or unwritten and never read as results).
 // Parameter gradients are ACCUMULATED into the caller's fp32 buffers (flat optimizer buffer or zeroed temporaries).
 #include "../../include/gdmae_hip.h"
 #include "common.h"
@@ -262,16 +271,8 @@ int splitk_for(long long n_pad, int m, int k) {
   while ((long long)S * 2 <= lim && n_pad % (S * 2) == 0) S *= 2;
   return S;
 }
-// dW (m, k) fp32 += G^T (m, n_pad) X (n_pad, k): S batched partial products + reduce-accumulate
-int linear_dw(const Ctx& c, const void* G, const void* X, float* dW, long long n_pad, int m, int k, float* part) {
-  const int S = splitk_for(n_pad, m, k);
-  const long long kc = n_pad / S;
-  GD_TRY(gd_gemm(c.st, false, true, k, m, (int)kc, X, k, G, m, part, k, c.ty, HIP_R_32F, nullptr, S, kc * k, kc * m, (long long)m * k,
-                 c.lt_ws, kLtWorkspace));
-  GD_TRY(gd_splitk_acc(c.st, part, S, (long long)m * k, dW, 1));
-  return 0;
-}
-// the same with the reduce deferred: the partial products go to their own region and the job is appended to J
+// dW (m, k) fp32 += G^T (m, n_pad) X (n_pad, k): S batched partial products into their own region; the reduce-accumulate is
+// appended to J (all of a layer's reduces are one launch at its end)
 int linear_dw_deferred(const Ctx& c, const void* G, const void* X, float* dW, long long n_pad, int m, int k, float* part,
                        SplitkJobs& J) {
   const int S = splitk_for(n_pad, m, k);
@@ -358,8 +359,8 @@ Saved saved_layout(void* base, long long n_pad, int d, int ff, int es) {
   return s;
 }
 struct Scratch {
-  char *lt_ws, *dx1_res, *dfb, *s2, *dg, *dh, *dx1_b, *dx_res, *dab, *s1, *d_o, *dqk, *dv, *apart, *dtau, *dx_qk, *dx_v, *part, *ln_ws,
-      *cs_part, *part_w[5], *ln_ws2, *ln_ws2b;
+  char *lt_ws, *dx1_res, *dfb, *dg, *dh, *dx1_b, *dx_res, *dab, *d_o, *dqk, *dv, *apart, *dtau, *dx_qk, *dx_v, *ln_ws, *cs_part,
+      *part_w[5], *ln_ws2, *ln_ws2b;
   size_t bytes;
 };
 Scratch scratch_layout(void* base, long long n_pad, int d, int ff, int es, int nhead) {
@@ -369,15 +370,12 @@ Scratch scratch_layout(void* base, long long n_pad, int d, int ff, int es, int n
   auto take = [&](size_t b) { char* p = (char*)base + off; off += gd_align(b); return p; };
   const size_t rd = (size_t)n_pad * d, rf = (size_t)n_pad * ff;
   s.lt_ws = take(kLtWorkspace);
-  s.dx1_res = take(rd * 4); s.dfb = es == 2 ? take(rd * es) : s.dx1_res; s.s2 = take((size_t)3 * d * 4);
+  s.dx1_res = take(rd * 4); s.dfb = es == 2 ? take(rd * es) : s.dx1_res;
   s.dg = take(rf * es); s.dh = take(rf * es); s.dx1_b = take(rd * es);
-  s.dx_res = take(rd * 4); s.dab = es == 2 ? take(rd * es) : s.dx_res; s.s1 = take((size_t)3 * d * 4);
+  s.dx_res = take(rd * 4); s.dab = es == 2 ? take(rd * es) : s.dx_res;
   s.d_o = take(rd * es); s.dqk = take(2 * rd * es); s.dv = take(rd * es);
   s.apart = take((size_t)(n_attn_items > 0 ? n_attn_items : 1) * 4); s.dtau = take(256);
   s.dx_qk = take(rd * es); s.dx_v = take(rd * es);
-  size_t mk = (size_t)ff * d;
-  if ((size_t)2 * d * d > mk) mk = (size_t)2 * d * d;
-  s.part = take((size_t)256 * mk * 4);      // S * m * k <= 1024 tiles * 128 * 128 ... bounded by 256 * m * k
   {   // LayerNorm-backward partial rows: the row kernel writes <= 1024 of them, the fused GEMM epilogue one per 32-row workgroup
     size_t lnb = gdmae_add_layernorm_workspace_bytes(d);
     const size_t fused_rows = (size_t)(n_pad / 32) * 3 * d * sizeof(float);
@@ -421,13 +419,10 @@ int gd_ln_partial_rows(long long n, int d);
 
 // fused token GEMMs (tok_gemm.hip)
 void gd_attn_timing_tokens(long long n);   // attention.hip: token count for the byte figure of the next attention entry
-bool gd_tok_gemm_supported(int K, int N);
 int gd_tok_gemm_plain(hipStream_t st, const void* X, const void* Wp, const void* bias, long long n_pad, int K, int N, void* out);
 int gd_tok_gemm_qkv(hipStream_t st, const void* Xpos, const void* X, const void* Wp_qk, const void* Wp_v, const void* bias3,
                     long long n_pad, int d, void* qk, void* v);
-int gd_tok_gemm_gelu(hipStream_t st, const void* X, const void* Wp, const void* bias, long long n_pad, int K, int N, void* h, void* gact);
 int gd_tok_gemm_gelu_bwd(hipStream_t st, const void* dY, const void* Wp, const void* h, long long n_pad, int K, int N, void* dh, void* gact);
-bool gd_tok_gemm_ffn_supported(int d, int ff);
 int gd_tok_gemm_ffn(hipStream_t st, const void* X, const void* W1p, const void* b1, const void* W2p, const void* b2, long long n,
                     long long n_pad, int d, void* h, const float* res, const float* gamma, const float* beta, float eps, float* y,
                     float* stats, void* y_bf, const float* pos_table, const int* tok_pos, void* ypos_bf, void* f_out);
@@ -472,42 +467,29 @@ Packed packed_layout(const void* base, int d, int ff) {
   p.bytes = off;
   return p;
 }
-bool use_fused(const gdmae_layer_args* a) {
-  static const int off = getenv("GDMAE_TOKGEMM") ? atoi(getenv("GDMAE_TOKGEMM")) == 0 : 0;
-  return !off && a->bf16 && a->packed != nullptr && a->d <= 256 && gd_tok_gemm_supported(a->d, a->ff) &&
-         gd_tok_gemm_supported(a->ff, a->d) && gd_tok_gemm_supported(a->d, 2 * a->d) && gd_tok_gemm_supported(a->d, a->d) &&
-         gd_tok_gemm_supported(2 * a->d, a->d);
+enum Schedule { LIBRARY, PER_PRODUCT, FUSED };
+// The one decision: the hand-written token kernels serve bf16 rows with a packed weight image at d in {128, 256}, ff = 2 d (both
+// PER_PRODUCT and FUSED; which of the two is the caller's args.path), everything else runs on the library GEMMs.
+Schedule layer_schedule(const gdmae_layer_args* a) {
+  if (!(a->bf16 && a->packed != nullptr && gd_layer_fused_supported(a->d, a->ff))) return LIBRARY;
+  return a->path == 1 ? FUSED : PER_PRODUCT;
 }
-bool use_grouped_dw(const gdmae_layer_args* a, long long n_pad) {
-  static const int off = getenv("GDMAE_DWGROUP") ? atoi(getenv("GDMAE_DWGROUP")) == 0 : 0;
-  return !off && a->bf16 && gd_dw_group_supported(n_pad, a->d, a->ff);
-}
-// feed-forward block as one forward launch (gelu(h) is then produced by the BACKWARD's GELU kernel, which runs before the grouped
-// weight-gradient launch - not before the per-matrix one)
-bool use_ffn(const gdmae_layer_args* a, long long n_pad) {
-  static const int off = getenv("GDMAE_FFN") ? atoi(getenv("GDMAE_FFN")) == 0 : 0;
-  return !off && use_fused(a) && use_grouped_dw(a, n_pad) && gd_tok_gemm_ffn_supported(a->d, a->ff);
-}
-// the stage as three fused launches per layer and direction around the attention, bf16 residual stream (layer_fused.hip);
-// GDMAE_LAYER_V2=0: the launch-per-product sequence with the fp32 stream (A/B reference)
-int g_layer_path = -1;      // -1: GDMAE_LAYER_V2 (default on), 0: launch-per-product, 1: fused (gdmae_encoder_set_layer_path)
-bool stage_v2(const gdmae_layer_args* layers, int n_layers) {
-  static const int env_off = getenv("GDMAE_LAYER_V2") ? atoi(getenv("GDMAE_LAYER_V2")) == 0 : 0;
-  if (g_layer_path == 0 || (g_layer_path < 0 && env_off)) return false;
-  for (int i = 0; i < n_layers; ++i)
-    if (!(use_ffn(&layers[i], pad_rows(layers[i].n)) && gd_layer_fused_supported(layers[i].d, layers[i].ff))) return false;
-  return true;
-}
+// gdmae_encoder_set_layer_path: what gdmae_encoder_stage_fused answers for supported layers (-1 = 1).  Read there and nowhere else:
+// the path a forward ran travels in args.path to its backward.
+int g_layer_path = -1;
 }  // namespace
 
 extern "C" int gdmae_encoder_set_layer_path(int path) {
-  GD_REQUIRE(path >= -1 && path <= 1, "encoder_set_layer_path: -1 (environment default), 0 or 1");
+  GD_REQUIRE(path >= -1 && path <= 1, "encoder_set_layer_path: -1 (default: 1), 0 or 1");
   g_layer_path = path;
   return 0;
 }
 
 extern "C" int gdmae_encoder_stage_fused(const gdmae_layer_args* layers, int n_layers) {
-  return (layers != nullptr && n_layers >= 1 && stage_v2(layers, n_layers)) ? 1 : 0;
+  if (layers == nullptr || n_layers < 1 || g_layer_path == 0) return 0;
+  for (int i = 0; i < n_layers; ++i)
+    if (layer_schedule(&layers[i]) == LIBRARY) return 0;
+  return 1;
 }
 
 extern "C" size_t gdmae_layer_packed_bytes(int d, int ff) { return packed_layout(nullptr, d, ff).bytes; }
@@ -545,25 +527,47 @@ extern "C" int gdmae_encoder_layer_bytes(long long n, int d, int ff, int nhead, 
   return 0;
 }
 
-// One layer forward.  `next` (bf16 mode only): the layer that consumes this one's output - its q/k and v inputs
-// (x, x + pos in bf16) are then written by this layer's second LayerNorm pass; `prepped`: this layer's inputs were
-// written that way by the previous layer (its gdmae_prep_tokens pass is skipped).
-static int layer_fwd(const gdmae_layer_args* a, const gdmae_layer_args* next, bool prepped, void* stream) {
+namespace {
+// what every entry point requires of a layer; PER_PRODUCT and FUSED end in the grouped weight-gradient launch, which n_pad (a
+// multiple of 2048) and their widths always allow
+int check_layer(const gdmae_layer_args* a) {
   GD_REQUIRE(a->n > 0 && a->d % 8 == 0 && a->ff % 8 == 0, "encoder layer: bad sizes");
   GD_REQUIRE(a->n_levels >= 1 && a->n_levels <= 4, "encoder layer: 1..4 window levels");
+  GD_REQUIRE(a->path == 0 || a->path == 1, "encoder layer: path is 0 or 1");
+  GD_REQUIRE(layer_schedule(a) == LIBRARY || gd_dw_group_supported(pad_rows(a->n), a->d, a->ff), "encoder layer: grouped weight gradients");
+  return 0;
+}
+// a stage: layers that share n, d, ff, dtype, schedule; FUSED needs path = 1 on layers the fused kernels serve
+int check_stage(const gdmae_layer_args* layers, int n_layers) {
+  GD_REQUIRE(layers != nullptr && n_layers >= 1, "encoder stage: no layers");
+  for (int i = 0; i < n_layers; ++i) {
+    GD_TRY(check_layer(&layers[i]));
+    GD_REQUIRE(layers[i].n == layers[0].n && layers[i].d == layers[0].d && layers[i].ff == layers[0].ff && layers[i].bf16 == layers[0].bf16 &&
+                   layers[i].path == layers[0].path && layer_schedule(&layers[i]) == layer_schedule(&layers[0]),
+               "encoder stage: layers must share n, d, ff, dtype, path and schedule");
+  }
+  GD_REQUIRE(layers[0].path == 0 || layer_schedule(&layers[0]) == FUSED,
+             "encoder stage: path 1 needs bf16 rows, packed weights, d in {128, 256}, ff = 2 d (gdmae_encoder_stage_fused)");
+  return 0;
+}
+}  // namespace
+
+// ---- LIBRARY schedule.  `next` (bf16 mode only): the layer that consumes this one's output - its q/k and v inputs
+// (x, x + pos in bf16) are then written by this layer's second LayerNorm pass; `prepped`: this layer's inputs were
+// written that way by the previous layer (its gdmae_prep_tokens pass is skipped).
+static int layer_lib_fwd(const gdmae_layer_args* a, const gdmae_layer_args* next, bool prepped, void* stream) {
   const long long n = a->n, n_pad = pad_rows(n);
   const int d = a->d, ff = a->ff, es = a->bf16 ? 2 : 4;
   Ctx c{(hipStream_t)stream, a->bf16 ? HIP_R_16BF : HIP_R_32F, es, a->scratch};
   Saved s = saved_layout(a->saved, n_pad, d, ff, es);
-  // pad rows of every GEMM operand: zero
+  // pad rows of every GEMM operand: zero (the split-K weight gradients run over all n_pad rows)
   ZeroJobs z;
   z.count = 0;
   add_zero(z, s.xb, n, n_pad, (long long)d * es);
   add_zero(z, s.xpb, n, n_pad, (long long)d * es);
   add_zero(z, s.o, n, n_pad, (long long)d * es);
   add_zero(z, s.x1b, n, n_pad, (long long)d * es);   // fp32 mode: x1 itself
-  // (the grouped weight-gradient kernel does not read rows >= n, and every other consumer is row-wise)
-  if (!use_grouped_dw(a, n_pad)) GD_TRY(zero_regions(c, z));
+  GD_TRY(zero_regions(c, z));
   if (a->bf16) {
     if (!prepped) GD_TRY(gdmae_prep_tokens(a->x, a->pos_table, a->tok_pos, n, d, s.xb, s.xpb, 1, stream));
   } else {
@@ -572,41 +576,11 @@ static int layer_fwd(const gdmae_layer_args* a, const gdmae_layer_args* next, bo
   }
   const char* Win = (const char*)a->Win;
   const char* bin = (const char*)a->bin;
-  const bool fused = use_fused(a);
-  const Packed pk = packed_layout(a->packed, d, ff);
-  if (fused) {
-    GD_TRY(gd_tok_gemm_qkv(c.st, s.xpb, s.xb, pk.qk, pk.v, bin, n_pad, d, s.qk, s.v));
-  } else {
-    GD_TRY(linear_fwd(c, s.xpb, Win, bin, s.qk, n_pad, 2 * d, d));
-    GD_TRY(linear_fwd(c, s.xb, Win + (size_t)2 * d * d * es, bin + (size_t)2 * d * es, s.v, n_pad, d, d));
-  }
+  GD_TRY(linear_fwd(c, s.xpb, Win, bin, s.qk, n_pad, 2 * d, d));
+  GD_TRY(linear_fwd(c, s.xb, Win + (size_t)2 * d * d * es, bin + (size_t)2 * d * es, s.v, n_pad, d, d));
   gd_attn_timing_tokens(n);
   GD_TRY(gdmae_window_attention_levels_fwd(s.qk, s.v, s.o, a->bf16, a->csr_tok, a->win_start, a->win_len, a->n_levels, a->n_win,
                                            a->max_tokens, d, a->nhead, a->tau, a->tau_min, (float*)s.lse, stream));
-  if (fused) {
-    // out-projection + residual + LayerNorm 1; linear1 + GELU; linear2 + residual + LayerNorm 2 (+ the next layer's
-    // q/k/v operands): three launches for what is eight in the unfused sequence
-    GD_TRY(gd_tok_gemm_res_ln(c.st, s.o, pk.o, a->bo, n, n_pad, d, d, a->x, a->g1, a->be1, a->eps, (float*)s.x1, (float*)s.st1, s.x1b,
-                              nullptr, nullptr, nullptr, s.a, 1));      // x1 is the residual operand of the very next launch
-    // linear1 + GELU + linear2 + residual + LayerNorm 2 in one launch when the widths allow it: gelu(h) never leaves the CU (the
-    // backward's GELU kernel writes it into s.gact for the weight gradient of linear2)
-    const bool ffn1 = use_ffn(a, n_pad);
-    if (!ffn1) GD_TRY(gd_tok_gemm_gelu(c.st, s.x1b, pk.w1, a->b1, n_pad, d, ff, s.h, s.gact));
-    void *y_bf = nullptr, *ypos_bf = nullptr;
-    const float* ptab = nullptr;
-    const int* tpos = nullptr;
-    if (next) {
-      Saved sn = saved_layout(next->saved, n_pad, d, ff, es);
-      y_bf = sn.xb; ypos_bf = sn.xpb; ptab = next->pos_table; tpos = next->tok_pos;
-    }
-    if (ffn1)
-      GD_TRY(gd_tok_gemm_ffn(c.st, s.x1b, pk.w1, a->b1, pk.w2, a->b2, n, n_pad, d, s.h, (const float*)s.x1, a->g2, a->be2, a->eps, a->y,
-                             (float*)s.st2, y_bf, ptab, tpos, ypos_bf, s.f));
-    else
-      GD_TRY(gd_tok_gemm_res_ln(c.st, s.gact, pk.w2, a->b2, n, n_pad, ff, d, (const float*)s.x1, a->g2, a->be2, a->eps, a->y,
-                                (float*)s.st2, y_bf, ptab, tpos, ypos_bf, s.f, 0));
-    return 0;
-  }
   GD_TRY(linear_fwd(c, s.o, a->Wo, a->bo, s.a, n_pad, d, d));
   GD_TRY(gdmae_add_layernorm_fwd(a->x, s.a, a->bf16, a->g1, a->be1, n, d, a->eps, (float*)s.x1, (float*)s.st1,
                                  a->bf16 ? s.x1b : nullptr, stream));
@@ -623,10 +597,34 @@ static int layer_fwd(const gdmae_layer_args* a, const gdmae_layer_args* next, bo
   return 0;
 }
 
-extern "C" int gdmae_encoder_layer_fwd(const gdmae_layer_args* a, void* stream) { return layer_fwd(a, nullptr, false, stream); }
+// ---- PER_PRODUCT schedule: in-projection; attention; out-projection + residual + LayerNorm 1; linear1 + GELU + linear2 + residual +
+// LayerNorm 2 (+ the q/k/v operands of `next`): four launches around the attention.  No kernel of this schedule reads a row >= n as
+// a result and the grouped weight-gradient launch ignores them: nothing to zero.  gelu(h) never leaves the CU (the backward's GELU
+// kernel writes it into s.gact for the weight gradient of linear2).  `next` / `prepped` as in layer_lib_fwd.
+static int layer_tok_fwd(const gdmae_layer_args* a, const gdmae_layer_args* next, bool prepped, void* stream) {
+  const long long n = a->n, n_pad = pad_rows(n);
+  const int d = a->d, ff = a->ff;
+  hipStream_t st = (hipStream_t)stream;
+  Saved s = saved_layout(a->saved, n_pad, d, ff, 2);
+  const Packed pk = packed_layout(a->packed, d, ff);
+  if (!prepped) GD_TRY(gdmae_prep_tokens(a->x, a->pos_table, a->tok_pos, n, d, s.xb, s.xpb, 1, stream));
+  GD_TRY(gd_tok_gemm_qkv(st, s.xpb, s.xb, pk.qk, pk.v, a->bin, n_pad, d, s.qk, s.v));
+  gd_attn_timing_tokens(n);
+  GD_TRY(gdmae_window_attention_levels_fwd(s.qk, s.v, s.o, 1, a->csr_tok, a->win_start, a->win_len, a->n_levels, a->n_win,
+                                           a->max_tokens, d, a->nhead, a->tau, a->tau_min, (float*)s.lse, stream));
+  GD_TRY(gd_tok_gemm_res_ln(st, s.o, pk.o, a->bo, n, n_pad, d, d, a->x, a->g1, a->be1, a->eps, (float*)s.x1, (float*)s.st1, s.x1b,
+                            nullptr, nullptr, nullptr, s.a, 1));      // x1 is the residual operand of the very next launch
+  void *y_bf = nullptr, *ypos_bf = nullptr;
+  const float* ptab = nullptr;
+  const int* tpos = nullptr;
+  if (next) {
+    Saved sn = saved_layout(next->saved, n_pad, d, ff, 2);
+    y_bf = sn.xb; ypos_bf = sn.xpb; ptab = next->pos_table; tpos = next->tok_pos;
+  }
+  return gd_tok_gemm_ffn(st, s.x1b, pk.w1, a->b1, pk.w2, a->b2, n, n_pad, d, s.h, (const float*)s.x1, a->g2, a->be2, a->eps, a->y,
+                         (float*)s.st2, y_bf, ptab, tpos, ypos_bf, s.f);
+}
 
-// L consecutive layers of one stage (same n, d, ff; layer i + 1 reads layer i's y): one call, and in bf16 mode the
-// prep_tokens pass of layers 1.. is folded into the previous layer's second LayerNorm.
 // The stage with the fused layer launches (layer_fused.hip): per layer q/k/v projections, attention, ONE launch for everything
 // behind it.  The residual stream between the layers is the bf16 row the next layer's v projection reads anyway (xb of its saved
 // block); only the last layer writes the fp32 rows the caller sees.
@@ -634,7 +632,6 @@ static int stage_fwd_v2(const gdmae_layer_args* layers, int n_layers, void* stre
   hipStream_t st = (hipStream_t)stream;
   for (int i = 0; i < n_layers; ++i) {
     const gdmae_layer_args* a = &layers[i];
-    GD_REQUIRE(a->n > 0 && a->n_levels >= 1 && a->n_levels <= 4, "encoder layer: bad sizes");
     const long long n = a->n, n_pad = pad_rows(n);
     const int d = a->d, ff = a->ff;
     Saved s = saved_layout(a->saved, n_pad, d, ff, 2);
@@ -661,24 +658,27 @@ static int stage_fwd_v2(const gdmae_layer_args* layers, int n_layers, void* stre
   return 0;
 }
 
+extern "C" int gdmae_encoder_layer_fwd(const gdmae_layer_args* a, void* stream) {
+  GD_TRY(check_layer(a));
+  GD_REQUIRE(a->path == 0, "encoder layer: path 1 is a stage call");
+  return layer_schedule(a) == LIBRARY ? layer_lib_fwd(a, nullptr, false, stream) : layer_tok_fwd(a, nullptr, false, stream);
+}
+
+// L consecutive layers of one stage (same n, d, ff): one call.  path 0: layer i + 1 reads layer i's y (x[i] == y[i-1]) and in bf16
+// mode the prep_tokens pass of layers 1.. is folded into the previous layer's second LayerNorm; path 1: stage_fwd_v2.
 extern "C" int gdmae_encoder_stage_fwd(const gdmae_layer_args* layers, int n_layers, void* stream) {
-  GD_REQUIRE(n_layers >= 1, "encoder stage: no layers");
-  for (int i = 0; i < n_layers; ++i)
-    GD_REQUIRE(i == 0 || (layers[i].x == layers[i - 1].y && layers[i].n == layers[0].n && layers[i].d == layers[0].d &&
-                          layers[i].ff == layers[0].ff && layers[i].bf16 == layers[0].bf16),
-               "encoder stage: layers must chain (x[i] = y[i-1]) and share n, d, ff, dtype");
-  if (stage_v2(layers, n_layers)) return stage_fwd_v2(layers, n_layers, stream);
-  GD_REQUIRE(n_layers == 1 || (uintptr_t)layers[1].x >= 4096, "encoder stage: chained by tokens (the fused path's convention) but the fused path is off");
+  GD_TRY(check_stage(layers, n_layers));
+  if (layers[0].path == 1) return stage_fwd_v2(layers, n_layers, stream);
   GD_REQUIRE(!layers[0].x_bf16 && !layers[n_layers - 1].res_out, "encoder stage: bf16 input rows / the folded block residual need the fused path");
+  const bool lib = layer_schedule(&layers[0]) == LIBRARY;
   for (int i = 0; i < n_layers; ++i) {
-    GD_REQUIRE(i == 0 || (layers[i].x == layers[i - 1].y && layers[i].n == layers[0].n && layers[i].d == layers[0].d &&
-                          layers[i].ff == layers[0].ff && layers[i].bf16 == layers[0].bf16),
-               "encoder stage: layers must chain (x[i] = y[i-1]) and share n, d, ff, dtype");
-    GD_TRY(layer_fwd(&layers[i], i + 1 < n_layers ? &layers[i + 1] : nullptr, i > 0 && layers[i].bf16, stream));
+    GD_REQUIRE(i == 0 || layers[i].x == layers[i - 1].y, "encoder stage: layers must chain (x[i] = y[i-1])");
+    const gdmae_layer_args* next = i + 1 < n_layers ? &layers[i + 1] : nullptr;
+    const bool prepped = i > 0 && layers[i].bf16;
+    GD_TRY(lib ? layer_lib_fwd(&layers[i], next, prepped, stream) : layer_tok_fwd(&layers[i], next, prepped, stream));
   }
   return 0;
 }
-
 
 namespace {
 // The five weight gradients + three bias column sums of a layer as ONE grouped launch, then the tail launch that reduces their
@@ -747,21 +747,18 @@ int grouped_dw_and_tail(const gdmae_layer_args* a, const Saved& s, const Scratch
 }
 }  // namespace
 
-// One layer backward.  `upstream3`: the upstream gradient is the sum of three tensors left in `scratch` by the
+// ---- LIBRARY schedule, backward.  `upstream3`: the upstream gradient is the sum of three tensors left in `scratch` by the
 // backward of the NEXT layer (its residual-stream gradient, dx_qk, dx_v - that layer skipped its add3 pass) instead of
 // a->dy; `defer_add3`: leave this layer's own three pieces in scratch for the previous layer the same way.
-// prev: the layer below (processed next) whose LayerNorm-2 backward is fused behind this layer's last input-gradient GEMM, or
-// null; ln2_done: this layer's own LayerNorm-2 backward was already produced that way by the layer above
-static int layer_bwd(const gdmae_layer_args* a, bool upstream3, bool defer_add3, const gdmae_layer_args* prev, bool ln2_done,
-                     void* stream) {
-  GD_REQUIRE(a->n > 0 && a->d % 8 == 0 && a->ff % 8 == 0, "encoder layer: bad sizes");
+static int layer_lib_bwd(const gdmae_layer_args* a, bool upstream3, bool defer_add3, void* stream) {
   const long long n = a->n, n_pad = pad_rows(n);
   const int d = a->d, ff = a->ff, es = a->bf16 ? 2 : 4;
-  long long items = 0;
-  for (int l = 0; l < a->n_levels; ++l) items += (long long)a->n_win[l] * a->nhead;
+  long long pbase = 0;                                 // attention partials: one per (window, head)
+  for (int l = 0; l < a->n_levels; ++l) pbase += (long long)a->n_win[l] * a->nhead;
   Saved s = saved_layout(a->saved, n_pad, d, ff, es);
   Scratch w = scratch_layout(a->scratch, n_pad, d, ff, es, a->nhead);
   Ctx c{(hipStream_t)stream, a->bf16 ? HIP_R_16BF : HIP_R_32F, es, w.lt_ws};
+  // the weight gradients are split-K GEMMs over all n_pad rows of zero-padded operands
   ZeroJobs z;
   z.count = 0;
   add_zero(z, w.dfb, n, n_pad, (long long)d * es);    // fp32 mode: dx1_res / dx_res themselves
@@ -769,18 +766,11 @@ static int layer_bwd(const gdmae_layer_args* a, bool upstream3, bool defer_add3,
   add_zero(z, w.dqk, n, n_pad, (long long)2 * d * es);
   add_zero(z, w.dv, n, n_pad, (long long)d * es);
   z.p[z.count] = w.apart;
-  z.n16[z.count] = (unsigned long long)(gd_align((size_t)(items > 0 ? items : 1) * 4) / 16);
+  z.n16[z.count] = (unsigned long long)(gd_align((size_t)(pbase > 0 ? pbase : 1) * 4) / 16);
   ++z.count;
-  // bf16 rows: the five weight gradients (and the three bias column sums that are not LayerNorm by-products) of the layer
-  // are ONE launch of the hand-written TN kernel at the end (dw_grouped.hip), which ignores rows >= n, and the attention
-  // kernels fill every partial slot of their level: nothing to clear.  fp32 rows / odd sizes: library split-K GEMMs over
-  // zero-padded operands.
-  const bool grouped = use_grouped_dw(a, n_pad);
-  if (!grouped) GD_TRY(zero_regions(c, z));
+  GD_TRY(zero_regions(c, z));
   // ---- LN2 and FFN
-  if (ln2_done) {
-    // dx1_res / dfb and the partial rows in ln_ws2 were written by the epilogue of the layer above's v-projection gradient
-  } else if (upstream3)   // dx_res / dx_qk / dx_v of the next layer are consumed here, before anything overwrites them
+  if (upstream3)   // dx_res / dx_qk / dx_v of the next layer are consumed here, before anything overwrites them
     GD_TRY(gd_add_layernorm_bwd_ex((const float*)s.x1, s.f, a->bf16, a->g2, (const float*)s.st2, (const float*)w.dx_res, w.dx_qk, a->bf16,
                                    w.dx_v, a->bf16, n, d, (float*)w.dx1_res, a->bf16 ? w.dfb : nullptr, nullptr, w.ln_ws2, c.st));
   else
@@ -788,86 +778,95 @@ static int layer_bwd(const gdmae_layer_args* a, bool upstream3, bool defer_add3,
                                    (float*)w.dx1_res, a->bf16 ? w.dfb : nullptr, nullptr, w.ln_ws2, c.st));
   SplitkJobs SJ;
   SJ.count = 0;
-  if (!grouped) GD_TRY(linear_dw_deferred(c, w.dfb, s.gact, a->dW2, n_pad, d, ff, (float*)w.part_w[0], SJ));
-  const bool fused = use_fused(a);
-  const Packed pk = packed_layout(a->packed, d, ff);
-  if (fused) {
-    // dh = (dfb W2) * gelu'(h); after the one-launch forward also gelu(h), the operand of linear2's weight gradient
-    GD_TRY(gd_tok_gemm_gelu_bwd(c.st, w.dfb, pk.w2t, s.h, n_pad, d, ff, w.dh, use_ffn(a, n_pad) ? s.gact : nullptr));
-  } else {
-    GD_TRY(linear_dx(c, w.dfb, a->W2, w.dg, n_pad, d, ff));
-    GD_TRY(gelu(c, false, w.dg, s.h, w.dh, n_pad * ff));
-  }
-  if (!grouped) GD_TRY(linear_dw_deferred(c, w.dh, s.x1b, a->dW1, n_pad, ff, d, (float*)w.part_w[1], SJ));
+  GD_TRY(linear_dw_deferred(c, w.dfb, s.gact, a->dW2, n_pad, d, ff, (float*)w.part_w[0], SJ));
+  GD_TRY(linear_dx(c, w.dfb, a->W2, w.dg, n_pad, d, ff));
+  GD_TRY(gelu(c, false, w.dg, s.h, w.dh, n_pad * ff));
+  GD_TRY(linear_dw_deferred(c, w.dh, s.x1b, a->dW1, n_pad, ff, d, (float*)w.part_w[1], SJ));
   // ---- LN1 (gradient = residual branch + FFN branch) and out-projection
-  const bool fuse_ln = fused && grouped;       // LayerNorm backward as the epilogue of the GEMM that produces its last gradient piece
-  if (fuse_ln) {
-    GD_TRY(gd_tok_gemm_ln_bwd(c.st, w.dh, pk.w1t, n, n_pad, ff, d, (const float*)w.dx1_res, nullptr, a->x, s.a, (const float*)s.st1, a->g1,
-                              (float*)w.dx_res, w.dab, (float*)w.ln_ws));
-  } else {
-    if (fused) GD_TRY(gd_tok_gemm_plain(c.st, w.dh, pk.w1t, nullptr, n_pad, ff, d, w.dx1_b));
-    else GD_TRY(linear_dx(c, w.dh, a->W1, w.dx1_b, n_pad, ff, d));
-    GD_TRY(gd_add_layernorm_bwd_ex(a->x, s.a, a->bf16, a->g1, (const float*)s.st1, (const float*)w.dx1_res, w.dx1_b, a->bf16, nullptr, 0,
-                                   n, d, (float*)w.dx_res, a->bf16 ? w.dab : nullptr, nullptr, w.ln_ws, c.st));
+  GD_TRY(linear_dx(c, w.dh, a->W1, w.dx1_b, n_pad, ff, d));
+  GD_TRY(gd_add_layernorm_bwd_ex(a->x, s.a, a->bf16, a->g1, (const float*)s.st1, (const float*)w.dx1_res, w.dx1_b, a->bf16, nullptr, 0,
+                                 n, d, (float*)w.dx_res, a->bf16 ? w.dab : nullptr, nullptr, w.ln_ws, c.st));
+  GD_TRY(linear_dw_deferred(c, w.dab, s.o, a->dWo, n_pad, d, d, (float*)w.part_w[2], SJ));
+  GD_TRY(linear_dx(c, w.dab, a->Wo, w.d_o, n_pad, d, d));
+  // ---- attention
+  gd_attn_timing_tokens(n);
+  GD_TRY(gdmae_window_attention_levels_bwd(s.qk, s.v, w.d_o, w.dqk, w.dv, a->bf16, (float*)w.apart, a->csr_tok, a->win_start, a->win_len,
+                                           a->n_levels, a->n_win, a->max_tokens, d, a->nhead, a->tau, a->tau_min, s.o, (const float*)s.lse, stream));
+  GD_TRY(gdmae_sum_partials_gated((const float*)w.apart, pbase, 1.f, (float*)w.dtau, a->tau, a->tau_min, stream));
+  GD_TRY(linear_dw_deferred(c, w.dqk, s.xpb, a->dWin, n_pad, 2 * d, d, (float*)w.part_w[3], SJ));
+  GD_TRY(linear_dw_deferred(c, w.dv, s.xb, a->dWin + (size_t)2 * d * d, n_pad, d, d, (float*)w.part_w[4], SJ));
+  GD_TRY(splitk_acc_jobs(c, SJ));                      // the five split-K reduces of the layer as one launch
+  ColsumJobs J;
+  J.count = 3;
+  J.x[0] = w.dh;  J.dst[0] = a->db1;           J.C[0] = ff;
+  J.x[1] = w.dqk; J.dst[1] = a->dbin;          J.C[1] = 2 * d;
+  J.x[2] = w.dv;  J.dst[2] = a->dbin + 2 * d;  J.C[2] = d;
+  GD_TRY(colsum_jobs(c, J, n, ff > 2 * d ? ff : 2 * d, (float*)w.cs_part));
+  // ---- LayerNorm / bias / temperature gradients from the LayerNorm backward partial rows
+  AccJobs j;
+  const int nb = gd_ln_partial_rows(n, d);
+  const float* p1 = (const float*)w.ln_ws;
+  const float* p2 = (const float*)w.ln_ws2;
+  float* dst[7] = {a->dg1, a->dbe1, a->dbo, a->dg2, a->dbe2, a->db2, a->dtau};
+  const float* src[7] = {p1, p1 + d, p1 + 2 * d, p2, p2 + d, p2 + 2 * d, (const float*)w.dtau};
+  int cols = 0;
+  for (int i = 0; i < 7; ++i) {
+    j.dst[i] = dst[i]; j.src[i] = src[i]; j.len[i] = i < 6 ? d : 1; j.nblk[i] = i < 6 ? nb : 0; j.stride[i] = 3 * d;
+    cols += j.len[i];
   }
-  if (!grouped) GD_TRY(linear_dw_deferred(c, w.dab, s.o, a->dWo, n_pad, d, d, (float*)w.part_w[2], SJ));
-  if (fused) GD_TRY(gd_tok_gemm_plain(c.st, w.dab, pk.ot, nullptr, n_pad, d, d, w.d_o));
-  else GD_TRY(linear_dx(c, w.dab, a->Wo, w.d_o, n_pad, d, d));
+  j.count = 7;
+  hipLaunchKernelGGL(k_acc_vectors, dim3((cols + 15) / 16), dim3(256), 0, c.st, j);
+  GD_LAUNCH_CHECK();
+  // ---- input gradient of the q/k and v projections
+  const char* Win = (const char*)a->Win;
+  GD_TRY(linear_dx(c, w.dqk, Win, w.dx_qk, n_pad, 2 * d, d));
+  GD_TRY(linear_dx(c, w.dv, Win + (size_t)2 * d * d * es, w.dx_v, n_pad, d, d));
+  if (!defer_add3) GD_TRY(gdmae_add3((const float*)w.dx_res, w.dx_qk, a->bf16, w.dx_v, a->bf16, n * d, a->dx, stream));
+  return 0;
+}
+
+// ---- PER_PRODUCT schedule, backward: every LayerNorm backward is the epilogue of the GEMM that produces its last gradient piece,
+// the five weight gradients + bias column sums are ONE grouped launch (which ignores rows >= n, and the attention kernels fill every
+// partial slot of their level: nothing to zero) reduced by the tail launch.
+// prev: the layer below (processed next) whose LayerNorm-2 backward runs behind this layer's last input-gradient GEMM, or null:
+// this layer then writes a->dx; ln2_done: this layer's own LayerNorm-2 backward (dx1_res / dfb, partial rows in ln_ws2) was
+// produced that way by the layer above, otherwise it is taken from a->dy by the row kernel.
+static int layer_tok_bwd(const gdmae_layer_args* a, const gdmae_layer_args* prev, bool ln2_done, void* stream) {
+  const long long n = a->n, n_pad = pad_rows(n);
+  const int d = a->d, ff = a->ff;
+  Saved s = saved_layout(a->saved, n_pad, d, ff, 2);
+  Scratch w = scratch_layout(a->scratch, n_pad, d, ff, 2, a->nhead);
+  Ctx c{(hipStream_t)stream, HIP_R_16BF, 2, w.lt_ws};
+  const Packed pk = packed_layout(a->packed, d, ff);
+  // ---- LN2 and FFN
+  if (!ln2_done)
+    GD_TRY(gd_add_layernorm_bwd_ex((const float*)s.x1, s.f, 1, a->g2, (const float*)s.st2, a->dy, nullptr, 0, nullptr, 0, n, d,
+                                   (float*)w.dx1_res, w.dfb, nullptr, w.ln_ws2, c.st));
+  // dh = (dfb W2) * gelu'(h), and gelu(h): the operand of linear2's weight gradient that the one-launch forward did not store
+  GD_TRY(gd_tok_gemm_gelu_bwd(c.st, w.dfb, pk.w2t, s.h, n_pad, d, ff, w.dh, s.gact));
+  // ---- LN1 (gradient = residual branch + FFN branch) and out-projection
+  GD_TRY(gd_tok_gemm_ln_bwd(c.st, w.dh, pk.w1t, n, n_pad, ff, d, (const float*)w.dx1_res, nullptr, a->x, s.a, (const float*)s.st1, a->g1,
+                            (float*)w.dx_res, w.dab, (float*)w.ln_ws));
+  GD_TRY(gd_tok_gemm_plain(c.st, w.dab, pk.ot, nullptr, n_pad, d, d, w.d_o));
   // ---- attention
   long long pbase = 0;
   for (int l = 0; l < a->n_levels; ++l) pbase += (long long)a->n_win[l] * a->nhead;
   gd_attn_timing_tokens(n);
-  GD_TRY(gdmae_window_attention_levels_bwd(s.qk, s.v, w.d_o, w.dqk, w.dv, a->bf16, (float*)w.apart, a->csr_tok, a->win_start, a->win_len,
+  GD_TRY(gdmae_window_attention_levels_bwd(s.qk, s.v, w.d_o, w.dqk, w.dv, 1, (float*)w.apart, a->csr_tok, a->win_start, a->win_len,
                                            a->n_levels, a->n_win, a->max_tokens, d, a->nhead, a->tau, a->tau_min, s.o, (const float*)s.lse, stream));
-  if (!grouped) GD_TRY(gdmae_sum_partials_gated((const float*)w.apart, pbase, 1.f, (float*)w.dtau, a->tau, a->tau_min, stream));
-  const char* Win = (const char*)a->Win;
-  const int nb_rows = gd_ln_partial_rows(n, d), nb_fused = (int)(n_pad / gd_tok_gemm_rows(d));
-  const int nb1 = fuse_ln ? nb_fused : nb_rows, nb2 = ln2_done ? nb_fused : nb_rows;
-  if (grouped) {
-    GD_TRY(grouped_dw_and_tail(a, s, w, c, n, n_pad, nb1, nb2, pbase));
-  } else {
-    GD_TRY(linear_dw_deferred(c, w.dqk, s.xpb, a->dWin, n_pad, 2 * d, d, (float*)w.part_w[3], SJ));
-    GD_TRY(linear_dw_deferred(c, w.dv, s.xb, a->dWin + (size_t)2 * d * d, n_pad, d, d, (float*)w.part_w[4], SJ));
-    GD_TRY(splitk_acc_jobs(c, SJ));                      // the five split-K reduces of the layer as one launch
-    ColsumJobs J;
-    J.count = 3;
-    J.x[0] = w.dh;  J.dst[0] = a->db1;           J.C[0] = ff;
-    J.x[1] = w.dqk; J.dst[1] = a->dbin;          J.C[1] = 2 * d;
-    J.x[2] = w.dv;  J.dst[2] = a->dbin + 2 * d;  J.C[2] = d;
-    GD_TRY(colsum_jobs(c, J, n, ff > 2 * d ? ff : 2 * d, (float*)w.cs_part));
-    // ---- LayerNorm / bias / temperature gradients from the LayerNorm backward partial rows
-    AccJobs j;
-    const float* p1 = (const float*)w.ln_ws;
-    const float* p2 = (const float*)w.ln_ws2;
-    float* dst[7] = {a->dg1, a->dbe1, a->dbo, a->dg2, a->dbe2, a->db2, a->dtau};
-    const float* src[7] = {p1, p1 + d, p1 + 2 * d, p2, p2 + d, p2 + 2 * d, (const float*)w.dtau};
-    int cols = 0;
-    for (int i = 0; i < 7; ++i) {
-      j.dst[i] = dst[i]; j.src[i] = src[i]; j.len[i] = i < 6 ? d : 1; j.nblk[i] = i < 3 ? nb1 : (i < 6 ? nb2 : 0); j.stride[i] = 3 * d;
-      cols += j.len[i];
-    }
-    j.count = 7;
-    hipLaunchKernelGGL(k_acc_vectors, dim3((cols + 15) / 16), dim3(256), 0, c.st, j);
-    GD_LAUNCH_CHECK();
+  // LayerNorm partial rows: one per workgroup of the GEMM epilogue, or those of the row kernel
+  const int nb_fused = (int)(n_pad / gd_tok_gemm_rows(d));
+  GD_TRY(grouped_dw_and_tail(a, s, w, c, n, n_pad, nb_fused, ln2_done ? nb_fused : gd_ln_partial_rows(n, d), pbase));
+  // ---- input gradient of the q/k and v projections (after the tail launch: the epilogue below re-uses ln_ws2)
+  GD_TRY(gd_tok_gemm_plain(c.st, w.dqk, pk.qkt, nullptr, n_pad, 2 * d, d, w.dx_qk));
+  if (prev) {
+    // ... and the LayerNorm-2 backward of the layer below: g = dx_res + dx_qk + bf16(dv Wv) is the gradient of its output
+    const Saved sp = saved_layout(prev->saved, n_pad, d, ff, 2);
+    return gd_tok_gemm_ln_bwd(c.st, w.dv, pk.vt, n, n_pad, d, d, (const float*)w.dx_res, w.dx_qk, (const float*)sp.x1, sp.f,
+                              (const float*)sp.st2, prev->g2, (float*)w.dx1_res, w.dfb, (float*)w.ln_ws2);
   }
-
-  // ---- input gradient of the q/k and v projections (after the tail launch: the fused epilogue below re-uses ln_ws2)
-  if (fused) {
-    GD_TRY(gd_tok_gemm_plain(c.st, w.dqk, pk.qkt, nullptr, n_pad, 2 * d, d, w.dx_qk));
-    if (fuse_ln && prev) {
-      // ... and the LayerNorm-2 backward of the layer below: g = dx_res + dx_qk + bf16(dv Wv) is the gradient of its output
-      const Saved sp = saved_layout(prev->saved, n_pad, d, ff, es);
-      GD_TRY(gd_tok_gemm_ln_bwd(c.st, w.dv, pk.vt, n, n_pad, d, d, (const float*)w.dx_res, w.dx_qk, (const float*)sp.x1, sp.f,
-                                (const float*)sp.st2, prev->g2, (float*)w.dx1_res, w.dfb, (float*)w.ln_ws2));
-      return 0;
-    }
-    GD_TRY(gd_tok_gemm_plain(c.st, w.dv, pk.vt, nullptr, n_pad, d, d, w.dx_v));
-  } else {
-    GD_TRY(linear_dx(c, w.dqk, Win, w.dx_qk, n_pad, 2 * d, d));
-    GD_TRY(linear_dx(c, w.dv, Win + (size_t)2 * d * d * es, w.dx_v, n_pad, d, d));
-  }
-  if (!defer_add3) GD_TRY(gdmae_add3((const float*)w.dx_res, w.dx_qk, a->bf16, w.dx_v, a->bf16, n * d, a->dx, stream));
-  return 0;
+  GD_TRY(gd_tok_gemm_plain(c.st, w.dv, pk.vt, nullptr, n_pad, d, d, w.dx_v));
+  return gdmae_add3((const float*)w.dx_res, w.dx_qk, 1, w.dx_v, 1, n * d, a->dx, stream);
 }
 
 // GDMAE_LAYER_TAIL_RIDES=0: the layer tails as launches of their own (A/B switch)
@@ -923,33 +922,24 @@ static int stage_bwd_v2(const gdmae_layer_args* layers, int n_layers, void* stre
 }
 
 extern "C" int gdmae_encoder_layer_bwd(const gdmae_layer_args* a, void* stream) {
-  return layer_bwd(a, false, false, nullptr, false, stream);
+  GD_TRY(check_layer(a));
+  GD_REQUIRE(a->path == 0, "encoder layer: path 1 is a stage call");
+  return layer_schedule(a) == LIBRARY ? layer_lib_bwd(a, false, false, stream) : layer_tok_bwd(a, nullptr, false, stream);
 }
 
-// Backward of gdmae_encoder_stage_fwd (layers in reverse); all layers MUST share one scratch buffer: the three pieces
-// of a layer's input gradient stay there and are summed on load by the previous layer's LayerNorm backward.
+// Backward of gdmae_encoder_stage_fwd (layers in reverse, the path of the forward in args.path); all layers MUST share one scratch
+// buffer: what a layer leaves for the one below (LIBRARY: the three pieces of its input gradient, summed on load by that layer's
+// LayerNorm backward; PER_PRODUCT / FUSED: that layer's finished LayerNorm-2 backward) stays there.
 // layers[n_layers - 1].dy = upstream gradient of the stage, layers[0].dx = gradient of the stage input.
 extern "C" int gdmae_encoder_stage_bwd(const gdmae_layer_args* layers, int n_layers, void* stream) {
-  GD_REQUIRE(n_layers >= 1, "encoder stage: no layers");
-  for (int i = 0; i < n_layers; ++i)
-    GD_REQUIRE(layers[i].scratch == layers[0].scratch && layers[i].n == layers[0].n && layers[i].d == layers[0].d &&
-                   layers[i].ff == layers[0].ff && layers[i].bf16 == layers[0].bf16,
-               "encoder stage: layers must share scratch, n, d, ff, dtype");
-  // The forward chose its path (gdmae_encoder_stage_fused) and laid the saved blocks out for it; on the fused path the caller chains the
-  // layers with small tokens instead of row pointers (x[i] = 1 + i).  A gdmae_encoder_set_layer_path call between a forward and its
-  // backward would send token "pointers" into the per-layer kernels, or fused kernels onto a launch-per-product saved block: refuse.
-  const bool tokens = n_layers > 1 && (uintptr_t)layers[1].x < 4096;
-  if (stage_v2(layers, n_layers)) {
-    GD_REQUIRE(n_layers == 1 || tokens, "encoder stage backward: the forward of these layers ran the launch-per-product path (layer path changed in between)");
-    return stage_bwd_v2(layers, n_layers, stream);
-  }
-  GD_REQUIRE(!tokens, "encoder stage backward: the forward of these layers ran the fused path (layer path changed in between)");
+  GD_TRY(check_stage(layers, n_layers));
+  for (int i = 0; i < n_layers; ++i) GD_REQUIRE(layers[i].scratch == layers[0].scratch, "encoder stage: layers must share scratch");
+  if (layers[0].path == 1) return stage_bwd_v2(layers, n_layers, stream);
   GD_REQUIRE(!layers[n_layers - 1].dres && !layers[0].dx_bf16, "encoder stage: the folded block residual needs the fused path");
-  // bf16 rows with packed weights: the LayerNorm-2 backward of layer i - 1 rides on layer i's last input-gradient GEMM
-  bool chain = true;
-  for (int i = 0; i < n_layers; ++i)
-    chain = chain && use_fused(&layers[i]) && use_grouped_dw(&layers[i], pad_rows(layers[i].n)) && layers[i].packed != nullptr;
-  for (int i = n_layers - 1; i >= 0; --i)
-    GD_TRY(layer_bwd(&layers[i], i + 1 < n_layers, i > 0, (chain && i > 0) ? &layers[i - 1] : nullptr, chain && i + 1 < n_layers, stream));
+  const bool lib = layer_schedule(&layers[0]) == LIBRARY;
+  for (int i = n_layers - 1; i >= 0; --i) {
+    const bool top = i + 1 == n_layers;
+    GD_TRY(lib ? layer_lib_bwd(&layers[i], !top, i > 0, stream) : layer_tok_bwd(&layers[i], i > 0 ? &layers[i - 1] : nullptr, !top, stream));
+  }
   return 0;
 }

@@ -1,24 +1,23 @@
-"""Hand-written forward/backward of one post-norm encoder layer.
+"""Forward/backward of one post-norm encoder layer, and of a whole stage of them.
 
 Same arithmetic as ``EncoderLayer.forward`` of the reference (pcdet/models/model_utils/sst_basic_block.py:77-84 with
 ``WindowAttention`` :22-54 and the cosine attention of cosine_msa.py): q = k = x + pos, v = x, packed in-projection
 used as separate q/k and v slices, windowed cosine attention, out-projection, LN(x + attn), FFN with GELU(erf),
 LN(x + ffn).  What differs is only the schedule: at 20-40 k tokens per stage every kernel of the layer runs for
-5-30 us, so the step is bound by launch granularity.  Going through autograd op by op costs ~140 launches per layer
-(dtype casts, bias-gradient reductions, gradient accumulation adds, split-K tails); this Function issues ~55:
+5-30 us, so the step is bound by launch granularity, and autograd op by op costs ~140 launches per layer.
 
-* one ``gdmae_prep_tokens`` writes x and x + pos in the GEMM dtype (instead of an add and two casts);
-* the fused add+LayerNorm kernels emit the bf16 copy the next GEMM needs, accept the second gradient branch on load
-  (no accumulation kernels) and return the column sums that are the bias gradient of the preceding GEMM;
-* activations that are operands of a weight-gradient GEMM live in buffers padded to a multiple of 2048 rows (pad
-  rows zero), so dW = g^T x is ONE batched GEMM over K-chunks + one reduction, without a tail GEMM;
-* the residual-stream gradient is assembled by one ``gdmae_add3``.
-GEMMs are hipBLASLt through torch (bf16 under autocast, fp32 otherwise); attention, LayerNorm, prep/add kernels are
-libgdmae_hip.so.
+* ``EncoderStageFn`` / ``EncoderLayerNativeFn`` (the product): one C-ABI call per stage or layer and direction into
+  csrc/encoder_layer.hip, which picks the schedule - for bf16 rows at d in {128, 256}, ff = 2 d the library's own token-GEMM
+  kernels on packed weight images (a stage: three fused launches per layer and direction around the attention, or with
+  ``gdmae_encoder_set_layer_path(0)`` one launch per product), otherwise hipBLASLt products + row kernels.  The stage asks
+  ``gdmae_encoder_stage_fused`` once, before its forward, and hands the answer to both directions in ``LayerArgs.path``.
+* ``EncoderLayerFn`` (``IMPL = "python"``, the op-by-op cross-check): the same hand-written backward with torch GEMMs (bf16
+  under autocast, fp32 otherwise) around libgdmae_hip.so's attention, LayerNorm and prep/add kernels: ``gdmae_prep_tokens`` writes
+  x and x + pos in the GEMM dtype, the add+LayerNorm kernels emit the bf16 copy the next GEMM needs and return the column sums
+  that are the bias gradient of the preceding GEMM, weight-gradient operands are padded to 2048 rows (dW = g^T x is one batched
+  GEMM over K-chunks + one reduction), the residual-stream gradient is one ``gdmae_add3``.
 """
 from __future__ import annotations
-
-import os
 
 import torch
 import torch.nn.functional as F
@@ -263,8 +262,8 @@ def _param_args(plist, cdt, direct):
     a = L.LayerArgs()
     for k, t in tensors.items():
         setattr(a, k, L.ptr(t))
-    if cdt == torch.bfloat16 and TOKGEMM:
-        # fragment-ordered weight image for the fused token GEMMs (refreshed by the optimizer for registered layers)
+    if cdt == torch.bfloat16:
+        # fragment-ordered weight image for the token-GEMM kernels (refreshed by the optimizer for registered layers)
         packed = (packing.registered if stable else packing.pack_now)(Win, Wo, W1, W2)
         if packed is not None:
             tensors["packed"] = packed
@@ -347,9 +346,7 @@ class EncoderLayerNativeFn(torch.autograd.Function):
 # ------------------------------------------------------------------------------------------------
 # stage executor: all layers of a stage (NUM_BLOCKS x 2) as ONE call per direction
 # ------------------------------------------------------------------------------------------------
-TOKGEMM = os.environ.get("GDMAE_TOKGEMM", "1") != "0"   # False: token GEMMs through hipBLASLt + separate row kernels (A/B)
-FOLD_RESIDUAL = os.environ.get("GDMAE_FOLD_RES", "1") != "0"   # False: the block residual as its own add pass behind the stage (A/B)
-STAGE = os.environ.get("GDMAE_STAGE", "1") != "0"     # False / GDMAE_STAGE=0: one call per layer (A/B reference)
+STAGE = True         # False: one call per layer (A/B reference)
 
 
 def _plist(layer):
@@ -389,19 +386,20 @@ class EncoderStageFn(torch.autograd.Function):
         for i in range(nl):
             arr[i].saved, arr[i].scratch = saved[i].data_ptr(), scratch.data_ptr()
         fused = bool(L.load().gdmae_encoder_stage_fused(arr, nl))
-        folded = fused and residual and x.dtype == torch.bfloat16 and FOLD_RESIDUAL
+        folded = fused and residual and x.dtype == torch.bfloat16
         if fused:
-            # only the last layer's output leaves the stage; x[i] == y[i-1] is the chaining contract of the entry point, the
-            # intermediate rows live in the layers' saved blocks
+            # only the first layer's input enters and the last layer's output leaves the stage: the rows in between live in the
+            # layers' saved blocks
             xin = x.contiguous() if folded else x.float().contiguous()
             out = torch.empty(n, d, dtype=torch.bfloat16 if folded else torch.float32, device=dev)
             for i in range(nl):
-                arr[i].x = xin.data_ptr() if i == 0 else 1 + i     # never dereferenced for i > 0; distinct tokens keep the chain check
-                arr[i].y = (2 + i) if i + 1 < nl else out.data_ptr()
+                arr[i].path = 1
+                arr[i].x = xin.data_ptr() if i == 0 else None
             if folded:
                 arr[0].x_bf16 = 1
                 arr[nl - 1].res_out = out.data_ptr()
-                arr[nl - 1].y = 0
+            else:
+                arr[nl - 1].y = out.data_ptr()
             ys = None
         else:
             xin = x.float().contiguous()
@@ -434,8 +432,8 @@ class EncoderStageFn(torch.autograd.Function):
             a = _call_args(bases[i][0], xin, wplans[i], pos_table, nhead, tau_min, eps, cdt, ff)
             a.saved, a.scratch = saved[i].data_ptr(), scratch.data_ptr()
             if fused:
-                a.x = xin.data_ptr() if i == 0 else 1 + i
-                a.y = 2 + i
+                a.path = 1
+                a.x = xin.data_ptr() if i == 0 else None
             else:
                 a.x = (xin if i == 0 else ys[i - 1]).data_ptr()
                 a.y = ys[i].data_ptr()

@@ -183,12 +183,13 @@ class _Stage:
             xin = x.contiguous() if folded else x.float().contiguous()
             out = res if folded else torch.empty(n, d, dtype=torch.float32, device=dev)
             for i in range(nl):
-                arr[i].x = xin.data_ptr() if i == 0 else 1 + i
-                arr[i].y = (2 + i) if i + 1 < nl else out.data_ptr()
+                arr[i].path = 1
+                arr[i].x = xin.data_ptr() if i == 0 else None
             if folded:
                 arr[0].x_bf16 = 1
                 arr[nl - 1].res_out = res.data_ptr()
-                arr[nl - 1].y = 0
+            else:
+                arr[nl - 1].y = out.data_ptr()
         else:
             xin = x.float().contiguous()
             ys = torch.empty(nl, n, d, dtype=torch.float32, device=dev)

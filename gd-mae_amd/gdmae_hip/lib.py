@@ -205,7 +205,7 @@ class LayerArgs(C.Structure):
                 + [(k, _P) for k in ("tok_pos", "csr_tok", "win_start", "win_len", "pos_table", "Win", "bin", "Wo", "bo", "W1", "b1",
                                      "W2", "b2", "g1", "be1", "g2", "be2", "tau", "x", "y", "dy", "dx", "dWin", "dbin", "dtau", "dWo",
                                      "dbo", "dW1", "db1", "dW2", "db2", "dg1", "dbe1", "dg2", "dbe2", "saved", "scratch", "packed")]
-                + [("x_bf16", _I), ("res_out", _P), ("dres", _P), ("dx_bf16", _P)])
+                + [("x_bf16", _I), ("res_out", _P), ("dres", _P), ("dx_bf16", _P), ("path", _I)])
 
 
 class PlanParams(C.Structure):

@@ -530,7 +530,8 @@ int gdmae_conv_block_bwd(const gdmae_conv_block_args* args /* host */, void* str
 /* ---- a13/a14 as one call: native executor of a whole encoder layer ------------------------------ *
  * EncoderLayer.forward (sst_basic_block.py:77-84; WindowAttention :22-54; cosine_msa.py): q = k = x + pos, v = x,
  * in-projection, windowed cosine attention, out-projection, LN(x + attn), FFN(GELU erf), LN(x + ffn) - forward or
- * backward enqueued by ONE call (hipBLASLt GEMMs with cached algorithms + the kernels above).  All pointers are
+ * backward enqueued by ONE call (the library's own token-GEMM kernels for bf16 rows with a packed weight image, d in
+ * {128, 256} and ff = 2 d; the gdmae_gemm products + the kernels above otherwise).  All pointers are
  * device pointers unless noted; weights and biases are in the GEMM dtype (bf16 != 0: bf16, else fp32), LayerNorm
  * parameters, tau, x, y, dy, dx and every parameter gradient are fp32.  Parameter gradients are ACCUMULATED (+=).
  * `saved` (gdmae_encoder_layer_bytes: saved_bytes) is written by the forward and read by the backward; `scratch`
@@ -556,11 +557,11 @@ typedef struct gdmae_layer_args {
   void* saved;
   void* scratch;
   /* bf16 mode, optional: the layer's weights packed in MFMA-fragment order by gdmae_tok_gemm_pack (layout:
-   * gdmae_layer_packed_bytes / gdmae_layer_pack_jobs).  Non-NULL: the token GEMMs that are not weight gradients run on
-   * the library's own fused kernels (gdmae_tok_gemm: bias + GELU, residual + LayerNorm, GELU backward in the epilogue)
-   * instead of hipBLASLt + separate row kernels. */
+   * gdmae_layer_packed_bytes / gdmae_layer_pack_jobs).  Non-NULL with d in {128, 256} and ff = 2 d: every product of the
+   * layer runs on the library's own kernels (gdmae_tok_gemm with bias / GELU / residual + LayerNorm epilogues, one grouped
+   * weight-gradient launch) instead of gdmae_gemm products + separate row kernels; with other widths it is ignored. */
   const void* packed;
-  /* Fused stage path only (gdmae_encoder_stage_fused() == 1), optional: the block residual around the stage (SSTBlockV1.forward,
+  /* Fused stage path only (path == 1), optional: the block residual around the stage (SSTBlockV1.forward,
    * spt_backbone.py:219-264: the stage output is added to the stage input before conv_out) folded into the stage's own launches,
    * all rows bf16.  Forward: layers[0].x_bf16 = 1 (x holds bf16 rows) and layers[n_layers-1].res_out = (n, d) bf16 receives
    * x + y instead of y.  Backward: layers[n_layers-1].dres = (n, d) bf16 gradient of res_out (read instead of dy; it is also the
@@ -569,6 +570,10 @@ typedef struct gdmae_layer_args {
   void* res_out;
   const void* dres;
   void* dx_bf16;
+  /* Launch sequence of a stage call, the same value in every layer of the call and in the backward as in its forward:
+   * 0 = one launch per product (or the gdmae_gemm sequence), 1 = the fused stage; see gdmae_encoder_set_layer_path.  1 is valid only
+   * where gdmae_encoder_stage_fused() answers 1; the single-layer entry points take 0. */
+  int path;
 } gdmae_layer_args;
 /* Packed weight image of one layer (bf16 mode): forward operands [Win(q,k rows) | Win(v rows) | Wo | W1 | W2] followed by
  * the transposed operands of the input-gradient products [W2^T | W1^T | Wo^T | Win(q,k)^T | Win(v)^T].
@@ -618,22 +623,25 @@ int gdmae_encoder_layer_bytes(long long n, int d, int ff, int nhead, int bf16, s
                               size_t* fwd_scratch_bytes, size_t* bwd_scratch_bytes);   /* depend on n only through ceil(n / 2048) */
 int gdmae_encoder_layer_fwd(const gdmae_layer_args* args /* host */, void* stream);
 int gdmae_encoder_layer_bwd(const gdmae_layer_args* args /* host */, void* stream);
-/* n_layers consecutive layers of one stage in one call (BasicShiftBlockV2 x NUM_BLOCKS, sst_basic_block.py:100-114):
- * layers[i+1].x == layers[i].y, same n / d / ff / dtype.  In bf16 mode the q/k and v inputs of layers 1.. are written
- * by the previous layer's second LayerNorm, and in the backward (all layers sharing ONE scratch buffer) the three
+/* n_layers consecutive layers of one stage in one call (BasicShiftBlockV2 x NUM_BLOCKS, sst_basic_block.py:100-114): same
+ * n / d / ff / dtype / path, and with path 0 layers[i+1].x == layers[i].y.  In bf16 mode the q/k and v inputs of layers 1.. are
+ * written by the previous layer's second LayerNorm, and in the backward (all layers sharing ONE scratch buffer) the three
  * pieces of a layer's input gradient are summed on load by the previous layer instead of being added and re-read.
- * Backward: layers[n_layers-1].dy = upstream gradient, layers[0].dx = gradient of the stage input. */
-int gdmae_encoder_stage_fwd(const gdmae_layer_args* layers /* host array */, int n_layers, void* stream);
-int gdmae_encoder_stage_bwd(const gdmae_layer_args* layers /* host array */, int n_layers, void* stream);
-/* Which launch sequence the stage entry points use for bf16 rows with packed weights (d in {128, 256}, ff = 2 d):
+ * Backward: layers[n_layers-1].dy = upstream gradient, layers[0].dx = gradient of the stage input.
+ * layers[i].path selects the launch sequence for bf16 rows with packed weights (d in {128, 256}, ff = 2 d):
  *   1  "layer around its bytes" (csrc/layer_fused.hip): per layer and direction THREE launches around the attention
  *      (forward: out-projection + LayerNorm 1 + feed-forward block + LayerNorm 2; backward: feed-forward block + LayerNorm 1 +
  *      out-projection, and in-projection + LayerNorm 2 of the layer below), bf16 residual stream inside the stage: 60 d bytes per
- *      token and layer instead of 106 d.  Only layers[n_layers-1].y (fp32) is written; the y of the other layers is not.
+ *      token and layer instead of 106 d.  Only layers[0].x is read and only layers[n_layers-1].y (fp32) is written; the x / y of
+ *      the layers in between are not used (NULL).  Refused for layers the fused kernels do not serve.
  *   0  one launch per product with fused row epilogues and an fp32 residual stream (csrc/tok_gemm.hip), every layers[i].y written.
- *  -1  the default: 1 unless the environment variable GDMAE_LAYER_V2 is 0. */
+ * The backward takes the path its forward took from the arguments alone. */
+int gdmae_encoder_stage_fwd(const gdmae_layer_args* layers /* host array */, int n_layers, void* stream);
+int gdmae_encoder_stage_bwd(const gdmae_layer_args* layers /* host array */, int n_layers, void* stream);
+/* What gdmae_encoder_stage_fused answers for layers the fused kernels serve: 1, 0, or -1 = the default (1). */
 int gdmae_encoder_set_layer_path(int path);
-/* 1 when gdmae_encoder_stage_fwd / _bwd would take the fused path (1 above) for these layers, else 0 */
+/* The path to write into layers[i].path: 1 when the fused stage serves these layers (and set_layer_path is not 0), else 0.
+ * Asked once, before the forward; neither stage entry point consults the setting. */
 int gdmae_encoder_stage_fused(const gdmae_layer_args* layers /* host array */, int n_layers);
 
 /* ---- a16: the decoder's ConvTranspose2d(k = s, stride s, no bias) blocks on token rows (csrc/rows_gemm.hip) ----------------- *

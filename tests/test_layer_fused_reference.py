@@ -425,7 +425,9 @@ def _poison(nbytes, dev):
     del t
 
 
-def _run_stage(case, path, dev):
+def _run_stage(case, path, dev, steps=2, path_before_backward=None):
+    """``steps`` identical steps of the stage under layer path ``path``; ``path_before_backward``: gdmae_encoder_set_layer_path is
+    called with it between each forward and its backward."""
     from gdmae_hip import configs, optim
     from gdmae_hip import encoder as genc
     from gdmae_hip import lib as glib
@@ -442,9 +444,9 @@ def _run_stage(case, path, dev):
     sb, fb, bb = genc._layer_bytes(n, d, 2 * d, NHEAD, 1)
     poison = nl * sb + fb + bb + 4 * n * d * 4 + (64 << 20)
     results = []
-    glib.call("gdmae_encoder_set_layer_path", path)
     try:
-        for _ in range(2):
+        for _ in range(steps):
+            glib.call("gdmae_encoder_set_layer_path", path)
             opt.zero_grad()
             xi = x.to(dev, xdt).requires_grad_(True)
             g = dy.to(dev, xdt)
@@ -453,6 +455,8 @@ def _run_stage(case, path, dev):
                 out = genc.encoder_stage([block], xi, pos_dev, wplans, residual=residual)
             assert out.grad_fn.meta[8] == (path == 1), "the stage did not take the requested layer path"
             _poison(poison, dev)
+            if path_before_backward is not None:
+                glib.call("gdmae_encoder_set_layer_path", path_before_backward)
             out.backward(g)
             torch.cuda.synchronize(dev)
             results.append((out.detach().clone(), xi.grad.detach().clone(), opt.flat_grad.clone(),
@@ -523,3 +527,24 @@ def test_encoder_stage_matches_fp64_reference(run):
     assert set(bound) == set(err)
     bad = [f"{k} = {v:.3e} > {bound[k]:.1e} ({w})" for k, (v, w) in err.items() if not v <= bound[k]]
     assert not bad, "; ".join(bad)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("path", [1, 0])
+@pytest.mark.parametrize("d,n", [(128, 70), (256, 33)], ids=["d128-n70", "d256-n33"])
+def test_backward_follows_the_path_of_its_forward(d, n, path):
+    """The layer path belongs to the call: the stage asks gdmae_encoder_stage_fused once, before its forward, and hands the answer
+    to both directions in the arguments.  A gdmae_encoder_set_layer_path call between a forward and its backward (forward under 1,
+    then 0; and forward under 0, then 1) therefore changes nothing: output, dx and the flat gradient of a two-layer stage are
+    bit-equal to the same step without the call.  n = 70 at d = 128 is past one 64-row tile, n = 33 at d = 256 past one 32-row
+    tile, both far below the 2048-row padding."""
+    dev = torch.device("cuda:0")
+    case = (d, n, 2, False, 0.6, ())
+    (o0, dx0, fg0, _), = _run_stage(case, path, dev, steps=1)
+    (o1, dx1, fg1, _), = _run_stage(case, path, dev, steps=1, path_before_backward=1 - path)
+    for name, t in (("y", o0), ("dx", dx0), ("flat gradient", fg0)):
+        assert bool(torch.isfinite(t).all()), f"{name} holds non-finite values"
+    assert float(fg0.abs().max()) > 0.0
+    assert torch.equal(o0, o1), "the output depends on a path set after the forward"
+    assert torch.equal(dx0, dx1), "dx depends on a path set between forward and backward"
+    assert torch.equal(fg0, fg1), "the flat gradient depends on a path set between forward and backward"
