@@ -18,6 +18,7 @@
 // Anchor geometry comes from small tables filled from the generated anchor tensor (the framework path's bits), not 7 floats per
 // anchor.  The IoU arithmetic restates box_utils.py:249-269 operation by operation; the build has -ffp-contract=off.
 // Anchor index: a = (y * W + x) * K + k, k = the anchor slot of a location (class-major, then size, then rotation).
+#include "anchor_decode.h"
 #include "common.h"
 
 namespace {
@@ -25,8 +26,6 @@ constexpr int kMaxGt = 512;       // ground-truth rows per sample the LDS copies
 constexpr int kMaxCls = 8;
 constexpr int kMaxSlots = 32;
 constexpr int kMaxBins = 8;
-
-__device__ __forceinline__ float ah_limit_period(float v, float offset, float period) { return v - floorf(v / period + offset) * period; }
 
 __device__ __forceinline__ float ah_iou(float ax1, float ay1, float ax2, float ay2, float area_a, float4 g, float area_g) {
   const float x_min = fmaxf(ax1, g.x), x_max = fminf(ax2, g.z);
@@ -511,29 +510,10 @@ __global__ __launch_bounds__(256) void k_ah_decode(AdArgs D) {
   };
   for (int c = 0; c < D.C; ++c) D.cls_out[e * D.C + c] = at(r0 + k * D.C + c);
   const long long b0 = r0 + D.K * D.C + k * 7;
-  const float* s = D.slot + k * 5;
-  const float xa = D.xc[x], ya = D.yc[y], za = s[0], dxa = s[1], dya = s[2], dza = s[3], ra = s[4];
-  const float diag = sqrtf(dxa * dxa + dya * dya);
+  const long long d0 = r0 + D.K * (D.C + 7) + k * D.nb;
   float o[7];
-  o[0] = at(b0 + 0) * diag + xa;
-  o[1] = at(b0 + 1) * diag + ya;
-  o[2] = at(b0 + 2) * dza + za;
-  o[3] = expf(at(b0 + 3)) * dxa;
-  o[4] = expf(at(b0 + 4)) * dya;
-  o[5] = expf(at(b0 + 5)) * dza;
-  o[6] = at(b0 + 6) + ra;
-  if (D.nb > 0) {
-    const long long d0 = r0 + D.K * (D.C + 7) + k * D.nb;
-    int best = 0;
-    float bv = at(d0);
-    for (int d = 1; d < D.nb; ++d) {
-      const float v = at(d0 + d);
-      if (v > bv) { bv = v; best = d; }
-    }
-    const float period = (float)(6.283185307179586 / (double)D.nb);
-    const float rot = ah_limit_period(o[6] - D.dir_offset, D.dir_limit_offset, period);
-    o[6] = (rot + D.dir_offset) + period * (float)best;
-  }
+  ah_decode_box([&](int i) { return at(b0 + i); }, [&](int d) { return at(d0 + d); }, D.nb, D.xc[x], D.yc[y], D.slot + k * 5, D.dir_offset,
+                D.dir_limit_offset, o);
 #pragma unroll
   for (int i = 0; i < 7; ++i) D.boxes[e * 7 + i] = o[i];
 }
@@ -569,11 +549,8 @@ __global__ __launch_bounds__(1024) void k_ah_select(const float* __restrict__ cl
     int arg = 0;
     bool ok = false;
     if (i < n) {
-      for (int c = 0; c < C; ++c) {
-        const float x = p[(long long)i * C + c];
-        const float s = normalized ? x : 1.f / (1.f + expf(-x));
-        if (c == 0 || s > best) { best = s; arg = c; }
-      }
+      const float* q = p + (long long)i * C;
+      ah_best_class([&](int c) { return q[c]; }, C, normalized, best, arg);
       ok = best >= thresh;
     }
     const unsigned long long m = __ballot(ok);

@@ -1,8 +1,13 @@
-"""Inference engine of the fine-tuned CenterPoint detector (DynVFE -> SPTBackbone -> SSTBEVBackbone -> CenterHead).
+"""Inference engine of the fine-tuned detectors: DynVFE -> SPTBackbone -> SSTBEVBackbone, then CenterHead (``CenterPoint``) or
+AnchorHeadSingle (``PointPillar``, the shipped KITTI fine-tune config).
 
-    engine = compile_detector(model)           # model: CenterPoint from build_network, .eval(), on the GPU
+    engine = compile_detector(model)           # model: CenterPoint / PointPillar from build_network, .eval(), on the GPU
     boxes, recall = engine(batch_dict)         # what model(batch_dict) returns in eval mode
     maps = engine.head_maps(batch_dict)        # per-head prediction maps (+ .spatial_features_2d, ...)
+
+The trunk (everything up to the channels-last bf16 BEV map) is shared; the head is a variant.  The anchor variant never writes the
+dense per-anchor arrays: ``gdmae_anchor_head_infer`` goes from the BEV map to the anchors at or above SCORE_THRESH (score, label,
+decoded box, in anchor order) in two launches, and the top-k / NMS tail of ``post_processing`` runs on those survivors only.
 
 In evaluation mode every BatchNorm is a constant per-channel affine: a = gamma / sqrt(running_var + eps), b = beta - a running_mean.
 ``compile_detector`` folds it into the weights of the product in front of it (W' = a W per output channel, computed in fp64 and
@@ -204,7 +209,8 @@ class _Stage:
 
 
 class HeadMaps(list):
-    """The per-head prediction dicts (what ``CenterHead.generate_predicted_boxes`` takes) plus the maps in front of them."""
+    """The per-head prediction dicts (what ``CenterHead.generate_predicted_boxes`` takes; for the anchor head one dict with the
+    ``cls_preds`` / ``box_preds`` / ``dir_cls_preds`` of its ``forward_ret_dict``) plus the maps in front of them."""
     spatial_features_2d = None
     spatial_features = None
     pillar_features = None
@@ -212,24 +218,29 @@ class HeadMaps(list):
 
 
 class DetectorEngine:
+    """The shared trunk; ``CenterPointEngine`` / ``AnchorEngine`` add the head."""
+
+    @staticmethod
+    def HEAD():
+        """the dense head class of the variant"""
+        raise NotImplementedError
+
+    def _refresh_head(self, dev):
+        raise NotImplementedError
+
     def __init__(self, model):
-        from pcdet.models.detectors.centerpoint import CenterPoint
         from pcdet.models.backbones_3d.vfe.dyn_vfe import DynVFE
         from pcdet.models.backbones_3d.spt_backbone import SPTBackbone
         from pcdet.models.backbones_2d.sst_bev_backbone import SSTBEVBackbone
-        from pcdet.models.dense_heads.center_head import CenterHead
-        if not isinstance(model, CenterPoint):
-            _no(f"compile_detector covers the CenterPoint detector, not {type(model).__name__}")
+        if not next(model.parameters()).is_cuda:       # what is not covered first (NotImplementedError), then how it is called
+            _no("the model must be on the GPU (the CenterPoint / PointPillar engines run on the library's kernels only)")
         if model.training:
             raise ValueError("gdmae_hip.inference: compile_detector needs the model in evaluation mode (call model.eval() first)")
-        for name, kind in (("vfe", DynVFE), ("backbone_3d", SPTBackbone), ("backbone_2d", SSTBEVBackbone), ("dense_head", CenterHead)):
+        for name, kind in (("vfe", DynVFE), ("backbone_3d", SPTBackbone), ("backbone_2d", SSTBEVBackbone), ("dense_head", self.HEAD())):
             if not isinstance(getattr(model, name, None), kind):
                 _no(f"model.{name} must be a {kind.__name__}")
         if getattr(model, "roi_head", None) is not None or getattr(model, "point_head", None) is not None:
             _no("two-stage heads")
-        p0 = next(model.parameters())
-        if not p0.is_cuda:
-            _no("the model must be on the GPU")
         self.model = model
         self.refresh()
 
@@ -310,7 +321,81 @@ class DetectorEngine:
                 _no("BEV block input width does not follow the block before it")
             self.bev.append((_Dense(conv, bn, True), conv.out_channels == c and i in m.backbone_2d.conv_shortcut))
             c = conv.out_channels
-        # head
+        self.bev_out = c
+        self._refresh_head(dev)
+        self._stamped = stamp
+        return self
+
+    # ---- one forward -----------------------------------------------------------------------------------------------
+    def _trunk(self, batch_dict):
+        """-> (B, x2 (B, H, W, c) channels-last bf16 BEV map, sf: the decoder's map, pillar features, the voxelisation).  Called under
+        no_grad and with autocast disabled."""
+        from pcdet.models.backbones_3d.spt_backbone import stage_plan_args
+        m = self.model
+        vfe, bb = m.vfe, m.backbone_3d
+        B = int(batch_dict['batch_size'])
+        vox = batch_dict.get('_gdmae_vox', None)
+        if vox is None:
+            vox = gplan.voxelize(batch_dict['points'], vfe.point_cloud_range, vfe.voxel_size, vfe.grid_size, B)
+        if not 3 <= vox.n_cols - 1 <= 5 or vox.points_pm is None:
+            _no("points with 3 to 5 features in pillar-major order")
+        dev = vox.voxel_coords.device
+        pf = torch.empty(vox.M, 128, dtype=torch.float32, device=dev)
+        w1, b1, w2, b2 = self.vfe_w
+        L.call("gdmae_vfe_infer", L.ptr(vox.points_pm), L.ptr(vox.voxel_coords), L.ptr(vox.row_pillar), L.ptr(vox.pillar_mean), int(vox.N),
+               int(vox.M), vox.n_cols, L.host_f32(vox.lo), L.host_f32(vox.vs), L.ptr(w1), L.ptr(b1), 64, L.ptr(w2), L.ptr(b2), 128, L.ptr(pf),
+               L.stream())
+        ep = gplan.encoder_plan(vox, *stage_plan_args(bb.model_cfg.SST_BLOCK_LIST), keep_frac=None)
+        x, si, hidden = pf, 0, []
+        for down, stage, conv_out in self.stages:
+            if down is not None:
+                si += 1
+                x = down(x, ep.stages[si].nbr_down)
+            sp = ep.stages[si]
+            x = conv_out(stage(x, sp.windows), sp.nbr_subm)
+            hidden.append((x, sp))
+        # decoder: the concatenated map = the constant row everywhere + relu(P' + b_i) at the sites the tokens cover
+        srcs = [hidden[i] for i in self.dec_sources]
+        s0 = self.deblocks[0][4]
+        Y, X = srcs[0][1].Y * s0, srcs[0][1].X * s0
+        ctot = self.dec_bg.numel()
+        Z = torch.empty(B * Y * X, ctot, dtype=BF16, device=dev)
+        L.call("gdmae_fill_rows", L.ptr(self.dec_bg), B * Y * X, ctot, 2, L.ptr(Z), L.stream())
+        col0 = 0
+        for (pf_img, b, cin, cout, s), (h, sp) in zip(self.deblocks, srcs):
+            if sp.Y * s != Y or sp.X * s != X or sp.B != B:
+                _no("decoder sources of different full-resolution sizes")
+            n = h.shape[0]
+            if n:
+                P = torch.empty(n * s * s, cout, dtype=BF16, device=dev)
+                L.call("gdmae_deconv_rows_fwd", L.ptr(h), n, cin, cout, s, L.ptr(pf_img), L.ptr(P), L.stream())
+                sites = gdec.upsampled_sites(sp, s, Y, X).contiguous()
+                L.call("gdmae_rows_affine_relu_scatter", L.ptr(P), 1, L.ptr(sites), n * s * s, cout, L.ptr(self.dec_ones), L.ptr(b), L.ptr(Z), 1,
+                       ctot, col0, L.stream())
+            col0 += cout
+        sf = self.dec_out(Z.view(B, Y, X, ctot))
+        x2 = sf
+        for conv, shortcut in self.bev:
+            x2 = conv(x2, x2 if shortcut else None)
+        return B, x2, sf, pf, vox
+
+    @staticmethod
+    def _with_maps(out: HeadMaps, x2, sf, pf, vox) -> HeadMaps:
+        out.spatial_features_2d = x2.permute(0, 3, 1, 2)
+        out.spatial_features = sf.permute(0, 3, 1, 2)
+        out.pillar_features = pf
+        out.voxel_coords = vox.voxel_coords
+        return out
+
+
+class CenterPointEngine(DetectorEngine):
+    @staticmethod
+    def HEAD():
+        from pcdet.models.dense_heads.center_head import CenterHead
+        return CenterHead
+
+    def _refresh_head(self, dev):
+        m, c = self.model, self.bev_out
         hd = m.dense_head
         conv, bn = _block(hd.shared_conv, nn.Conv2d)
         self.shared = _Dense(conv, bn, True)
@@ -335,61 +420,12 @@ class DetectorEngine:
                     _no(f"head branch {name}: channel widths do not chain")
                 branches.append((name, ops))
             self.heads.append(branches)
-        self._stamped = stamp
-        return self
 
-    # ---- one forward -----------------------------------------------------------------------------------------------
     @torch.no_grad()
     def head_maps(self, batch_dict) -> HeadMaps:
         self._check_fresh()
-        from pcdet.models.backbones_3d.spt_backbone import stage_plan_args
-        m = self.model
-        vfe, bb = m.vfe, m.backbone_3d
-        B = int(batch_dict['batch_size'])
-        vox = batch_dict.get('_gdmae_vox', None)
-        if vox is None:
-            vox = gplan.voxelize(batch_dict['points'], vfe.point_cloud_range, vfe.voxel_size, vfe.grid_size, B)
-        if not 3 <= vox.n_cols - 1 <= 5 or vox.points_pm is None:
-            _no("points with 3 to 5 features in pillar-major order")
-        dev = vox.voxel_coords.device
         with torch.autocast("cuda", enabled=False):
-            pf = torch.empty(vox.M, 128, dtype=torch.float32, device=dev)
-            w1, b1, w2, b2 = self.vfe_w
-            L.call("gdmae_vfe_infer", L.ptr(vox.points_pm), L.ptr(vox.voxel_coords), L.ptr(vox.row_pillar), L.ptr(vox.pillar_mean), int(vox.N),
-                   int(vox.M), vox.n_cols, L.host_f32(vox.lo), L.host_f32(vox.vs), L.ptr(w1), L.ptr(b1), 64, L.ptr(w2), L.ptr(b2), 128, L.ptr(pf),
-                   L.stream())
-            ep = gplan.encoder_plan(vox, *stage_plan_args(bb.model_cfg.SST_BLOCK_LIST), keep_frac=None)
-            x, si, hidden = pf, 0, []
-            for down, stage, conv_out in self.stages:
-                if down is not None:
-                    si += 1
-                    x = down(x, ep.stages[si].nbr_down)
-                sp = ep.stages[si]
-                x = conv_out(stage(x, sp.windows), sp.nbr_subm)
-                hidden.append((x, sp))
-            # decoder: the concatenated map = the constant row everywhere + relu(P' + b_i) at the sites the tokens cover
-            srcs = [hidden[i] for i in self.dec_sources]
-            s0 = self.deblocks[0][4]
-            Y, X = srcs[0][1].Y * s0, srcs[0][1].X * s0
-            ctot = self.dec_bg.numel()
-            Z = torch.empty(B * Y * X, ctot, dtype=BF16, device=dev)
-            L.call("gdmae_fill_rows", L.ptr(self.dec_bg), B * Y * X, ctot, 2, L.ptr(Z), L.stream())
-            col0 = 0
-            for (pf_img, b, cin, cout, s), (h, sp) in zip(self.deblocks, srcs):
-                if sp.Y * s != Y or sp.X * s != X or sp.B != B:
-                    _no("decoder sources of different full-resolution sizes")
-                n = h.shape[0]
-                if n:
-                    P = torch.empty(n * s * s, cout, dtype=BF16, device=dev)
-                    L.call("gdmae_deconv_rows_fwd", L.ptr(h), n, cin, cout, s, L.ptr(pf_img), L.ptr(P), L.stream())
-                    sites = gdec.upsampled_sites(sp, s, Y, X).contiguous()
-                    L.call("gdmae_rows_affine_relu_scatter", L.ptr(P), 1, L.ptr(sites), n * s * s, cout, L.ptr(self.dec_ones), L.ptr(b), L.ptr(Z), 1,
-                           ctot, col0, L.stream())
-                col0 += cout
-            sf = self.dec_out(Z.view(B, Y, X, ctot))
-            x2 = sf
-            for conv, shortcut in self.bev:
-                x2 = conv(x2, x2 if shortcut else None)
+            B, x2, sf, pf, vox = self._trunk(batch_dict)
             xs = self.shared(x2)
             out = HeadMaps()
             for branches in self.heads:
@@ -400,11 +436,7 @@ class DetectorEngine:
                         y = op(y)
                     pd[name] = y[..., :ops[-1].cout].permute(0, 3, 1, 2)
                 out.append(pd)
-        out.spatial_features_2d = x2.permute(0, 3, 1, 2)
-        out.spatial_features = sf.permute(0, 3, 1, 2)
-        out.pillar_features = pf
-        out.voxel_coords = vox.voxel_coords
-        return out
+        return self._with_maps(out, x2, sf, pf, vox)
 
     @torch.no_grad()
     def __call__(self, batch_dict):
@@ -419,6 +451,111 @@ class DetectorEngine:
             return m.post_processing(bd)
 
 
+class AnchorEngine(DetectorEngine):
+    """``PointPillar`` with ``AnchorHeadSingle``: the three 1 x 1 convolutions, the score threshold and the box decoding of the
+    survivors are ``gdmae_anchor_head_infer`` (two launches); the tail of ``post_processing`` runs on the survivors."""
+
+    @staticmethod
+    def HEAD():
+        from pcdet.models.dense_heads.anchor_head_single import AnchorHeadSingle
+        return AnchorHeadSingle
+
+    def _check_post_cfg(self):
+        """the branches of ``post_processing`` this engine restates (its messages)"""
+        cfg = self.model.model_cfg.POST_PROCESSING
+        nms = cfg.NMS_CONFIG
+        if nms.MULTI_CLASSES_NMS:
+            raise NotImplementedError("MULTI_CLASSES_NMS: True (per-class NMS in post_processing) is not built")
+        if not nms.get('NMS', True) or cfg.get('OUTPUT_RAW_SCORE', False) or nms.NMS_TYPE != 'nms_gpu':
+            raise NotImplementedError("post_processing: only NMS_TYPE nms_gpu with OUTPUT_RAW_SCORE False is built")
+        if cfg.SCORE_THRESH is None:
+            _no("SCORE_THRESH: None (the anchor head's selection kernel needs a score threshold)")
+        return cfg
+
+    def _refresh_head(self, dev):
+        hd, cin = self.model.dense_head, self.bev_out
+        self._check_post_cfg()
+        if hd.conv_dir_cls is None:
+            _no("an anchor head without the direction classifier (USE_DIRECTION_CLASSIFIER)")
+        t = hd._device_tables(dev)             # refuses anchor sets with several bottom heights or different strides
+        K, C, nb = hd.num_anchors_per_location, hd.num_class, int(hd.model_cfg.NUM_DIR_BINS)
+        for conv, n_out in ((hd.conv_cls, K * C), (hd.conv_box, K * 7), (hd.conv_dir_cls, K * nb)):
+            if not (isinstance(conv, nn.Conv2d) and conv.kernel_size == (1, 1) and conv.stride == (1, 1) and conv.padding == (0, 0) and
+                    conv.groups == 1 and conv.in_channels == cin and conv.out_channels == n_out):
+                _no(f"anchor head convolution {conv} (1 x 1, {cin} -> {n_out})")
+        if cin % 32 != 0 or cin > 256:
+            _no(f"anchor head on a {cin}-channel map (the kernel reads multiples of 32 up to 256)")
+        if K * (C + 7 + nb) > 96 or C > 8 or nb > 8:
+            _no(f"anchor head too wide for the kernel: {K} anchors x ({C} + 7 + {nb}) = {K * (C + 7 + nb)} columns (96 at most)")
+        ws = [c.weight.detach().float().reshape(c.out_channels, cin).contiguous() for c in (hd.conv_cls, hd.conv_box, hd.conv_dir_cls)]
+        bs = [None if c.bias is None else c.bias.detach().float().contiguous() for c in (hd.conv_cls, hd.conv_box, hd.conv_dir_cls)]
+        self.head_packed = torch.empty(L.load().gdmae_anchor_head_infer_packed_bytes(cin), dtype=torch.uint8, device=dev)
+        L.call("gdmae_anchor_head_infer_pack", L.ptr(ws[0]), L.ptr(bs[0]), L.ptr(ws[1]), L.ptr(bs[1]), L.ptr(ws[2]), L.ptr(bs[2]), cin, K, C, nb,
+               L.ptr(self.head_packed), L.stream())
+        self.tables = t
+        self.K, self.C, self.nb, self.cin = K, C, nb, cin
+        self.dir_offset, self.dir_limit_offset = float(hd.model_cfg.DIR_OFFSET), float(hd.model_cfg.DIR_LIMIT_OFFSET)
+
+    def _head(self, x2, want_rows):
+        """-> (count (B), score (B, A), label (B, A), box (B, A, 7), rows (B H W, K (C + 7 + nb)) fp32 or None); the first count[b]
+        entries of a sample are written"""
+        B, H, W, c = x2.shape
+        t, K, C, nb = self.tables, self.K, self.C, self.nb
+        if (H, W) != (t['H'], t['W']) or c != self.cin:
+            _no(f"a {H} x {W} x {c} BEV map in front of an anchor head built for {t['H']} x {t['W']} x {self.cin}")
+        assert x2.dtype == BF16 and x2.is_contiguous()
+        dev, A = x2.device, H * W * K
+        thresh = float(self._check_post_cfg().SCORE_THRESH)
+        count = torch.empty(B, dtype=torch.int32, device=dev)
+        idx = torch.empty(B, A, dtype=torch.int32, device=dev)
+        score = torch.empty(B, A, dtype=torch.float32, device=dev)
+        label = torch.empty(B, A, dtype=torch.int32, device=dev)
+        box = torch.empty(B, A, 7, dtype=torch.float32, device=dev)
+        rows = torch.empty(B * H * W, K * (C + 7 + nb), dtype=torch.float32, device=dev) if want_rows else None
+        ws = torch.empty(L.load().gdmae_anchor_head_infer_workspace_bytes(B, H, W, K), dtype=torch.uint8, device=dev)
+        L.call("gdmae_anchor_head_infer", L.ptr(x2), B, H, W, c, K, C, nb, L.ptr(self.head_packed), L.ptr(t['xc']), L.ptr(t['yc']),
+               L.ptr(t['slot']), self.dir_offset, self.dir_limit_offset, thresh, L.ptr(rows), L.ptr(count), L.ptr(idx), L.ptr(score),
+               L.ptr(label), L.ptr(box), L.ptr(ws), L.stream())
+        return count, score, label, box, rows
+
+    @torch.no_grad()
+    def head_maps(self, batch_dict) -> HeadMaps:
+        self._check_fresh()
+        with torch.autocast("cuda", enabled=False):
+            B, x2, sf, pf, vox = self._trunk(batch_dict)
+            rows = self._head(x2, True)[4]
+        _, H, W, _ = x2.shape
+        K, C, nb = self.K, self.C, self.nb
+        r = rows.view(B, H, W, -1)
+        out = HeadMaps([{'cls_preds': r[..., :K * C], 'box_preds': r[..., K * C:K * (C + 7)], 'dir_cls_preds': r[..., K * (C + 7):]}])
+        return self._with_maps(out, x2, sf, pf, vox)
+
+    @torch.no_grad()
+    def __call__(self, batch_dict):
+        self._check_fresh()
+        m = self.model
+        with torch.autocast("cuda", enabled=False):
+            B, x2, _, _, _ = self._trunk(batch_dict)
+            count, score, label, box, _ = self._head(x2, False)
+            counts = count.tolist()                     # the one host read of the call: the output shapes depend on it
+            bd = {'batch_size': B}
+            if 'gt_boxes' in batch_dict:
+                bd['gt_boxes'] = batch_dict['gt_boxes']
+            recall_dict, pred_dicts = {}, []
+            for b in range(B):
+                n = counts[b]
+                pred, recall_dict = m.finish_sample(box[b, :n], score[b, :n], label[b, :n].long(), recall_dict, b, bd)
+                pred_dicts.append(pred)
+            return pred_dicts, recall_dict
+
+
 def compile_detector(model) -> DetectorEngine:
-    """Fold and pack ``model`` (a CenterPoint from ``pcdet.models.build_network``, in eval mode, on the GPU) for inference."""
-    return DetectorEngine(model)
+    """Fold and pack ``model`` (a CenterPoint or PointPillar from ``pcdet.models.build_network``, in eval mode, on the GPU) for
+    inference."""
+    from pcdet.models.detectors.centerpoint import CenterPoint
+    from pcdet.models.detectors.pointpillar import PointPillar
+    if isinstance(model, CenterPoint):
+        return CenterPointEngine(model)
+    if isinstance(model, PointPillar):
+        return AnchorEngine(model)
+    _no(f"compile_detector covers the CenterPoint and PointPillar detectors, not {type(model).__name__}")

@@ -188,6 +188,10 @@ SIGNATURES = {
     "gdmae_anchor_loss_bwd": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "gdmae_anchor_decode": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _F, _F, _P, _P, _P]),
     "gdmae_anchor_select": (_I, [_P, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P]),
+    "gdmae_anchor_head_infer_packed_bytes": (_Z, [_I]),
+    "gdmae_anchor_head_infer_pack": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P]),
+    "gdmae_anchor_head_infer_workspace_bytes": (_Z, [_I, _I, _I, _I]),
+    "gdmae_anchor_head_infer": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _F, _F, _F, _P, _P, _P, _P, _P, _P, _P, _P]),
     "gdmae_boxes_bev_pairs": (_I, [_P, _I, _P, _I, _I, _P, _P]),
     "gdmae_nms_workspace_bytes": (_Z, [_I]),
     "gdmae_nms_bev": (_I, [_P, _I, _F, _I, _P, _P, _P, _P]),

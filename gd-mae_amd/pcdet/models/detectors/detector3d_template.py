@@ -137,7 +137,6 @@ class Detector3DTemplate(nn.Module):
             raise NotImplementedError("batch_index (concatenated predictions) is not built in post_processing")
         if not nms.get('NMS', True) or cfg.get('OUTPUT_RAW_SCORE', False) or nms.NMS_TYPE != 'nms_gpu':
             raise NotImplementedError("post_processing: only NMS_TYPE nms_gpu with OUTPUT_RAW_SCORE False is built")
-        from ...ops.iou3d_nms import iou3d_nms_utils
         from gdmae_hip import lib as L
         cls_all, box_all = batch_dict['batch_cls_preds'], batch_dict['batch_box_preds']
         B = batch_dict['batch_size']
@@ -168,21 +167,32 @@ class Detector3DTemplate(nn.Module):
                 mask = sc_all >= thresh if thresh is not None else torch.ones_like(sc_all, dtype=torch.bool)
                 orig = mask.nonzero().view(-1)
                 scores, labels = sc_all[orig], lab_all[orig]
-            if scores.shape[0] > 0:
-                top_scores, top = torch.topk(scores, k=min(int(nms.NMS_PRE_MAXSIZE), scores.shape[0]))
-                keep, _ = iou3d_nms_utils.nms_gpu(box_preds[orig[top]][:, 0:7], top_scores, nms.NMS_THRESH)
-                sel = top[keep[:int(nms.NMS_POST_MAXSIZE)]]
-            else:
-                sel = torch.zeros(0, dtype=torch.int64, device=scores.device)
-            final_scores, final_labels, final_boxes = scores[sel], labels[sel], box_preds[orig[sel]]
-            ok = final_labels != 0
-            final_boxes, final_scores, final_labels = final_boxes[ok], final_scores[ok], final_labels[ok]
-            if cfg.get('RECALL_MODE', 'normal') == 'normal':
-                recall_dict = self.generate_recall_record(box_preds=final_boxes if 'rois' not in batch_dict else box_preds,
-                                                          recall_dict=recall_dict, batch_index=b, data_dict=batch_dict,
-                                                          thresh_list=cfg.RECALL_THRESH_LIST)
-            pred_dicts.append({'pred_boxes': final_boxes, 'pred_scores': final_scores, 'pred_labels': final_labels})
+            pred, recall_dict = self.finish_sample(box_preds[orig], scores, labels, recall_dict, b, batch_dict,
+                                                   all_boxes=box_preds if 'rois' in batch_dict else None)
+            pred_dicts.append(pred)
         return pred_dicts, recall_dict
+
+    def finish_sample(self, boxes, scores, labels, recall_dict, batch_index, batch_dict, all_boxes=None):
+        """The per-sample tail of ``post_processing`` on PRE-SELECTED anchors: ``boxes`` (m, 7+), ``scores`` (m), ``labels`` (m, int64,
+        1-based) of the anchors at or above SCORE_THRESH, in anchor order.  The NMS_PRE_MAXSIZE best, rotated NMS, NMS_POST_MAXSIZE,
+        the ``label != 0`` filter and the recall record (on ``all_boxes`` when RoIs are present).  -> (pred_dict, recall_dict)."""
+        from ...ops.iou3d_nms import iou3d_nms_utils
+        cfg = self.model_cfg.POST_PROCESSING
+        nms = cfg.NMS_CONFIG
+        if scores.shape[0] > 0:
+            top_scores, top = torch.topk(scores, k=min(int(nms.NMS_PRE_MAXSIZE), scores.shape[0]))
+            keep, _ = iou3d_nms_utils.nms_gpu(boxes[top][:, 0:7], top_scores, nms.NMS_THRESH)
+            sel = top[keep[:int(nms.NMS_POST_MAXSIZE)]]
+        else:
+            sel = torch.zeros(0, dtype=torch.int64, device=scores.device)
+        final_scores, final_labels, final_boxes = scores[sel], labels[sel], boxes[sel]
+        ok = final_labels != 0
+        final_boxes, final_scores, final_labels = final_boxes[ok], final_scores[ok], final_labels[ok]
+        if cfg.get('RECALL_MODE', 'normal') == 'normal':
+            recall_dict = self.generate_recall_record(box_preds=final_boxes if all_boxes is None else all_boxes,
+                                                      recall_dict=recall_dict, batch_index=batch_index, data_dict=batch_dict,
+                                                      thresh_list=cfg.RECALL_THRESH_LIST)
+        return {'pred_boxes': final_boxes, 'pred_scores': final_scores, 'pred_labels': final_labels}, recall_dict
 
     def forward(self, **kwargs):
         raise NotImplementedError

@@ -888,6 +888,23 @@ int gdmae_anchor_decode(const void* rows, int rows_bf16, int ld, int B, int H, i
 int gdmae_anchor_select(const float* cls, int B, int n, int C, int normalized, float thresh, int* idx, float* score, int* label,
                         int* count, void* stream);
 
+/* ---- anchor head at inference: BEV map -> survivors of the score threshold, two launches (csrc/anchor_head_infer.hip) -------- *
+ * X (B H W, cin) bf16 channels-last rows, cin % 32 == 0, cin <= 256; K (C + 7 + nb) <= 96 output columns.  pack: the three 1 x 1
+ * convolutions (fp32 device weights (K C | K 7 | K nb, cin) and biases, a null bias = 0) as ONE bf16 fragment image
+ * [cls | box | dir | zero padding to 96] followed by the fp32 bias; refreshed whenever the weights change.  The product accumulates
+ * in fp32 and the logits are never rounded; score / label / decode are the arithmetic of gdmae_anchor_select / gdmae_anchor_decode
+ * (csrc/anchor_decode.h), the box is decoded only for anchors with score >= thresh.  Per sample b: count[b], and the survivors in
+ * anchor order in idx / label (1-based) int32 (B, A), score (B, A), box (B, A, 7) fp32; nothing is written at or beyond count[b].
+ * rows_out (may be NULL): (B H W, K (C + 7 + nb)) fp32 logits of the same launch.  The result does not depend on scheduling. */
+size_t gdmae_anchor_head_infer_packed_bytes(int cin);
+int gdmae_anchor_head_infer_pack(const float* w_cls, const float* b_cls, const float* w_box, const float* b_box, const float* w_dir,
+                                 const float* b_dir, int cin, int K, int C, int nb, void* packed, void* stream);
+size_t gdmae_anchor_head_infer_workspace_bytes(int B, int H, int W, int K);
+int gdmae_anchor_head_infer(const void* X, int B, int H, int W, int cin, int K, int C, int nb, const void* packed, const float* xc,
+                            const float* yc, const float* slot, float dir_offset, float dir_limit_offset, float thresh,
+                            float* rows_out, int* count, int* idx, float* score, int* label, float* box, void* workspace,
+                            void* stream);
+
 /* ---- a21: fused optimizer step over one flat buffer ------------------------------------------- *
  * Replaces clip_grad_norm_ (tools/train_utils/train_utils.py:52) and OptimWrapper.step
  * (tools/train_utils/optimization/fastai_optim.py:135-152: p *= 1 - wd*lr, then torch Adam). */

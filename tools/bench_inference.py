@@ -1,8 +1,13 @@
-"""Inference timing of the config-D detector on one GPU: the engine (gdmae_hip.inference.compile_detector) against the model's own
-evaluation path (model.eval() under bf16 autocast and torch.no_grad()), same process, same seeded synthetic KITTI-shape frames, the
-two alternating, warm-up excluded, events around the timed loop and one sync after it.
+"""Inference timing of a fine-tuned detector on one GPU: the engine (gdmae_hip.inference.compile_detector) against the model's own
+evaluation path (model.eval() under bf16 autocast - and in fp32 with --fp32 - and torch.no_grad()), same process, same seeded
+synthetic KITTI-shape frames, the paths alternating, warm-up excluded, events around the timed loop and one sync after it.
 
-    python tools/bench_inference.py [--batches 1 8] [--runs 5] [--calls 10] [--warmup 3] [--path both|engine|parent]
+    python tools/bench_inference.py [--config D|kitti] [--batches 1 8] [--runs 5] [--calls 10] [--warmup 3] [--path both|engine|parent]
+
+--config D: the CenterPoint detector of config D (0.16 m pillars).  --config kitti: the PointPillar / AnchorHeadSingle detector of
+the shipped KITTI fine-tune config (configs.kitti_finetune_cfg(), 0.32 m pillars), conv_cls.bias set so that the scores straddle
+SCORE_THRESH; this run also times the head alone on the engine's bf16 BEV map: gdmae_anchor_head_infer (two launches) against the
+row product on the library GEMM + gdmae_anchor_decode + gdmae_anchor_select.
 
 Prints every run pair, the medians, frames/s, the kernel-launch count of one engine call and of one parent call (torch profiler,
 device activity), and the bytes of the encoder's backward-only side outputs one engine call writes.  --path engine | parent runs one
@@ -43,8 +48,49 @@ def launches(fn):
         return f"unavailable ({type(ex).__name__})"
 
 
+def head_alone(eng, net, pts, B, args):
+    """The anchor head alone on the engine's bf16 BEV map: the two-launch inference entry against the parent's evaluation head (row
+    product on the library GEMM under bf16 autocast, gdmae_anchor_decode, gdmae_anchor_select)."""
+    from gdmae_hip import lib as L
+    hd = net.dense_head
+    with torch.no_grad(), torch.autocast("cuda", enabled=False):
+        x2 = eng._trunk({"points": pts, "batch_size": B})[1]
+    sf2 = x2.permute(0, 3, 1, 2)
+    thresh = float(net.model_cfg.POST_PROCESSING.SCORE_THRESH)
+
+    def new():
+        with torch.no_grad():
+            return eng._head(x2, False)[0]
+
+    def old():
+        with torch.no_grad(), torch.autocast("cuda", dtype=torch.bfloat16):
+            d = hd({"spatial_features_2d": sf2, "batch_size": B})
+        cls = d["batch_cls_preds"]
+        n, C = cls.shape[1], cls.shape[2]
+        idx = torch.empty(B, n, dtype=torch.int32, device=cls.device)
+        score = torch.empty(B, n, dtype=torch.float32, device=cls.device)
+        label = torch.empty(B, n, dtype=torch.int32, device=cls.device)
+        count = torch.empty(B, dtype=torch.int32, device=cls.device)
+        L.call("gdmae_anchor_select", L.ptr(cls), B, n, C, 0, thresh, L.ptr(idx), L.ptr(score), L.ptr(label), L.ptr(count), L.stream())
+        return count
+    for fn in (new, old):
+        for _ in range(args.warmup):
+            fn()
+    torch.cuda.synchronize()
+    print(f"batch {B} head alone: survivors per sample, new {new().tolist()}  parent {old().tolist()}", flush=True)
+    res = {"new": [], "parent": []}
+    for r in range(args.runs):
+        res["new"].append(timed(new, args.calls))
+        res["parent"].append(timed(old, args.calls))
+        print(f"batch {B} head run {r}: new {res['new'][-1]:.3f} ms  parent {res['parent'][-1]:.3f} ms", flush=True)
+    a, b = statistics.median(res["new"]), statistics.median(res["parent"])
+    print(f"batch {B} head alone: new {a:.3f} ms, parent (gemm + decode + select) {b:.3f} ms, new / parent = {a / b:.3f}", flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--config", default="D", choices=["D", "kitti"])
+    ap.add_argument("--fp32", action="store_true", help="also time the parent's fp32 evaluation path")
     ap.add_argument("--batches", type=int, nargs="+", default=[8, 1])
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--calls", type=int, default=10)
@@ -53,7 +99,11 @@ def main():
     ap.add_argument("--no-launch-count", action="store_true", help="skip the in-process tracer (when an external kernel trace runs)")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
-    cfg, ds, skw = configs.named_config("D")
+    if args.config == "kitti":
+        cfg, ds = configs.kitti_finetune_cfg()
+        skw = dict(beams=32, azimuths=600, extra=800, features=4)
+    else:
+        cfg, ds, skw = configs.named_config("D")
     torch.manual_seed(3)
     net = build_network(cfg, len(ds.class_names), ds, logging.getLogger("bench")).to(dev).eval()
     g = torch.Generator().manual_seed(5)
@@ -62,6 +112,9 @@ def main():
             if isinstance(m, (torch.nn.BatchNorm1d, torch.nn.BatchNorm2d)):
                 m.running_mean.copy_(torch.randn(m.num_features, generator=g) * 0.2)
                 m.running_var.copy_(torch.rand(m.num_features, generator=g) + 0.5)
+        if args.config == "kitti":      # scores on both sides of SCORE_THRESH instead of the 0.01 prior of init_weights: the best-class
+            # logit of this seeded model without the bias spans -0.19 ... 0.33 (quartiles -0.11 / 0.08 / 0.27), the threshold is -0.847
+            net.dense_head.conv_cls.bias.fill_(-1.03)
     eng = inference.compile_detector(net)
     for B in args.batches:
         pts = torch.from_numpy(synth.synth_batch(100 + B, B, ds.point_cloud_range, **skw)).to(dev)
@@ -72,9 +125,14 @@ def main():
         def parent():
             with torch.no_grad(), torch.autocast("cuda", dtype=torch.bfloat16):
                 return net({"points": pts, "batch_size": B})
+        def parent_fp32():
+            with torch.no_grad():
+                return net({"points": pts, "batch_size": B})
         paths = [("engine", engine), ("parent", parent)]
         if args.path != "both":
             paths = [p for p in paths if p[0] == args.path]
+        if args.fp32 and args.path != "engine":
+            paths.append(("parent_fp32", parent_fp32))
         for _, fn in paths:
             for _ in range(args.warmup):
                 fn()
@@ -87,8 +145,11 @@ def main():
         for name, fn in paths:
             med = statistics.median(res[name])
             print(f"batch {B} {name}: median {med:.3f} ms per call, {B / med * 1e3:.1f} frames/s, launches per call {'-' if args.no_launch_count else launches(fn)}", flush=True)
-        if len(paths) == 2:
-            print(f"batch {B}: engine / parent median = {statistics.median(res['engine']) / statistics.median(res['parent']):.3f}", flush=True)
+        for other in ("parent", "parent_fp32"):
+            if "engine" in res and other in res:
+                print(f"batch {B}: engine / {other} median = {statistics.median(res['engine']) / statistics.median(res[other]):.3f}", flush=True)
+        if args.config == "kitti" and args.path == "both":
+            head_alone(eng, net, pts, B, args)
         if args.path != "parent" and not args.no_launch_count:
             maps = eng.head_maps({"points": pts, "batch_size": B})
             # backward-only side outputs of gdmae_encoder_stage_fwd (gdmae_encoder_layer_bytes: the `saved` block per layer)
