@@ -211,6 +211,10 @@ __device__ inline int win_level(const WinParams& P, int cnt) {
   return -1;
 }
 
+// One scan element = three 21-bit fields per word, one per occupancy level: `a` counts the windows of each level, `b` their
+// tokens.  LIMIT: the grand total of a field is the number of windows / tokens of one level, so both the window grid and the
+// stage's token count must stay below 2^21 or a level's prefix carries into the next level's field.  The window grid is refused
+// by the two entry points below; the token capacity is refused where it is known on the host (plan.hip, the plan layout).
 struct WinLoad {
   WinParams P;
   const int* win_cnt;

@@ -160,6 +160,9 @@ int layout(const gdmae_plan_params* p, gdmae_plan_buffer* table, int max_entries
     g.up_s = (us >= 1 && us * Y == gy && us * X == gx) ? us : 0;
     g.n_win = gd_plan_n_windows(B, Y, X, p->win_x[i], p->win_y[i]);
     GD_REQUIRE(g.n_win < (1 << 21), "geometry plan: window grid too large for the packed scan");
+    // a level's token prefix shares the 21-bit fields of the packed window scan (partition.hip, WinLoad): a stage that could hold
+    // 2^21 tokens could carry from one level's field into the next
+    GD_REQUIRE(g.cap < (1 << 21), "geometry plan: stage token capacity must stay below 2^21 (21-bit fields of the packed window scan)");
   }
   O.dec = p->n_dec > 0;
   for (int g = 0; g < p->n_dec; ++g) {

@@ -776,7 +776,10 @@ int gdmae_group_inner_inds(const long long* inverse_inds, long long n, long long
  * "counts" = int32 [N points kept, M pillars | tokens of stage 0.. | 8 per (stage, shift): windows per level (3), tokens per
  * level (3), windows, tokens | active tiles | visible pillars] - the only thing the host has to read back.
  * noise: (min(n_points, B*Y*X)) fp32 masking noise, one value per pillar in pillar order (null when !masked).
- * Outputs are bit-identical to the per-operator entry points above. */
+ * Outputs are bit-identical to the per-operator entry points above.
+ * Limits (refused by the layout): B*Y*X < 2^31; per stage, the window grid B * (ceil(X/wx) + 1) * (ceil(Y/wy) + 1) AND the token
+ * capacity (min(points, cells) for the first stage, min(4 * previous, cells) after a strided convolution) below 2^21 - the
+ * packed window scan keeps 21 bits per occupancy level. */
 #define GDMAE_PLAN_MAX_STAGES 4
 typedef struct gdmae_plan_params {
   long long n_points;          /* rows of `points` (capacity of every per-point / per-pillar buffer) */
