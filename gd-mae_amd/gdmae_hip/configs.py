@@ -119,6 +119,42 @@ def kitti_finetune_cfg():
     return m, SyntheticDatasetInfo(**KITTI)
 
 
+def graphrcnn_head_cfg():
+    """ROI_HEAD section of tools/cfgs/waymo_models/gd_mae_ts.yaml:264-320 (GraphRCNNHead).  The yaml spells the two empty NMS
+    sections as the string ``None``."""
+    return AttrDict({
+        'NAME': 'GraphRCNNHead', 'CLASS_AGNOSTIC': True,
+        'NMS_CONFIG': {'TRAIN': 'None', 'TEST': 'None'},
+        'DFVS_CONFIG': {'NUM_DVS_POINTS': 1024, 'NUM_FPS_POINTS': 256, 'HASH_SIZE': 4099, 'LAMBDA': 0.18, 'DELTA': 50,
+                        'POOL_EXTRA_WIDTH': [0.8, 0.8, 0.8], 'NUM_BOXES_PER_PATCH': 32},
+        'ATTN_GNN_CONFIG': {'IN_DIM': 11, 'OUT_DIM': 256, 'MLPS': [32, 32, 64], 'CALIB_DIM': 64, 'EXP_MLPS': [512], 'K': 8,
+                            'USE_FEATS_DIS': False, 'USE_REDUCTION': True, 'USE_SHORT_CUT': True},
+        'TARGET_CONFIG': {'BOX_CODER': 'ResidualCoder', 'BOX_CODER_CONFIG': {'norm': True}, 'ROI_PER_IMAGE': 128, 'FG_RATIO': 0.5,
+                          'SAMPLE_ROI_BY_EACH_CLASS': True, 'CLS_SCORE_TYPE': 'roi_iou', 'CLS_FG_THRESH': 0.75, 'CLS_BG_THRESH': 0.25,
+                          'CLS_BG_THRESH_LO': 0.1, 'HARD_BG_RATIO': 0.8, 'REG_FG_THRESH': 0.55},
+        'LOSS_CONFIG': {'CLS_LOSS': 'BinaryCrossEntropy', 'REG_LOSS': 'WeightedSmoothL1Loss', 'CORNER_LOSS_REGULARIZATION': True,
+                        'LOSS_WEIGHTS': {'rcnn_cls_weight': 1.0, 'rcnn_reg_weight': 1.0, 'rcnn_corner_weight': 1.0,
+                                         'code_weights': [1.0] * 7}},
+    })
+
+
+def waymo_two_stage_cfg():
+    """MODEL section of the shipped two-stage config (tools/cfgs/waymo_models/gd_mae_ts.yaml:76-331): GraphRCNN detector =
+    DynVFE -> SPTBackbone -> SSTBEVBackbone -> CenterHead (per-class NMS, RoIs for refining) -> GraphRCNNHead, post-processing
+    without NMS.  -> (model_cfg, dataset_info)."""
+    ssl = gdmae_ssl_model_cfg(0.0)
+    head = center_head_cfg()
+    head.POST_PROCESSING.NMS_CONFIG = AttrDict({'NMS_TYPE': 'multi_class_nms', 'NMS_THRESH': [0.7, 0.55, 0.55],
+                                                'NMS_PRE_MAXSIZE': [2048, 1024, 1024], 'NMS_POST_MAXSIZE': [200, 150, 150],
+                                                'IOU_RECTIFIER': [0., 0., 0.]})
+    m = AttrDict({'NAME': 'GraphRCNN', 'FREEZE_LAYERS': ['DynVFE', 'SPTBackbone', 'SSTBEVBackbone', 'CenterHead'],
+                  'VFE': ssl.VFE, 'BACKBONE_3D': gdmae_finetune_backbone_cfg(), 'BACKBONE_2D': sst_bev_backbone_cfg(),
+                  'DENSE_HEAD': head, 'ROI_HEAD': graphrcnn_head_cfg(),
+                  'POST_PROCESSING': {'RECALL_THRESH_LIST': [0.3, 0.5, 0.7], 'OUTPUT_RAW_SCORE': False, 'EVAL_METRIC': 'waymo_custom',
+                                      'NMS_CONFIG': {'MULTI_CLASSES_NMS': False, 'NMS': False}}})
+    return m, SyntheticDatasetInfo(**WAYMO)
+
+
 def optimization_cfg(batch_size_per_gpu=8, num_epochs=30):
     """OPTIMIZATION section of the ssl yamls (gd_mae_ssl.yaml:183-203)."""
     return AttrDict({'BATCH_SIZE_PER_GPU': batch_size_per_gpu, 'NUM_EPOCHS': num_epochs, 'OPTIMIZER': 'adam_onecycle',

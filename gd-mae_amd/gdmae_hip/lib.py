@@ -200,6 +200,8 @@ SIGNATURES = {
     "gdmae_grad_sq_norm": (_I, [_P, _L, _P, _P, _P]),
     "gdmae_adam_step": (_I, [_P, _P, _P, _P, _P, _I, _F, _F, _F, _F, _F, _I, _F, _F, _P, _P]),
     "gdmae_adam_step_shadow": (_I, [_P, _P, _P, _P, _P, _I, _F, _F, _F, _F, _F, _I, _F, _F, _P, _P, _P]),
+    "gdmae_roi_dfvs_pool_workspace_bytes": (_Z, [_L, _I, _I, _I, _I]),
+    "gdmae_roi_dfvs_pool": (_I, [_P, _L, _I, _P, _I, _I, _I, _P, _P, _I, _I, _P, _I, _I, _I, _F, _F, _I, _I, _P, _P, _P, _P, _P, _Z, _P]),
 }
 
 class LayerArgs(C.Structure):

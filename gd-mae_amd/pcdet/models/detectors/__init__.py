@@ -1,6 +1,7 @@
 from .detector3d_template import Detector3DTemplate
 from .centerpoint import CenterPoint
 from .gd_mae import GDMAE
+from .graph_rcnn import GraphRCNN
 from .pointpillar import PointPillar
 
 __all__ = {
@@ -8,6 +9,7 @@ __all__ = {
     'GDMAE': GDMAE,
     'CenterPoint': CenterPoint,
     'PointPillar': PointPillar,
+    'GraphRCNN': GraphRCNN,
 }
 
 

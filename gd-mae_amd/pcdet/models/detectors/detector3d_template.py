@@ -1,14 +1,14 @@
 """Model-builder subset of the reference ``Detector3DTemplate``
 (pcdet/models/detectors/detector3d_template.py:14-100, 361-442): the ``module_topology`` walk with the
 same keyword calls into the name->class registries, ``global_step``, and checkpoint loading by
-key+shape.  Builders for modules outside the GD-MAE pre-training path return ``None`` unless their yaml
+key+shape, the RoI head of the two-stage config included.  Builders for modules outside the built paths return ``None`` unless their yaml
 section is present, in which case they raise (nothing is silently skipped)."""
 import os
 
 import torch
 import torch.nn as nn
 
-from .. import backbones_2d, backbones_3d, dense_heads
+from .. import backbones_2d, backbones_3d, dense_heads, roi_heads
 from ..backbones_3d import vfe
 
 
@@ -91,6 +91,16 @@ class Detector3DTemplate(nn.Module):
         model_info_dict['module_list'].append(m)
         return m, model_info_dict
 
+    def build_roi_head(self, model_info_dict):
+        if self.model_cfg.get('ROI_HEAD', None) is None:
+            return None, model_info_dict
+        m = roi_heads.__all__[self.model_cfg.ROI_HEAD.NAME](
+            model_cfg=self.model_cfg.ROI_HEAD, input_channels=model_info_dict['num_point_features'],
+            backbone_channels=model_info_dict.get('backbone_channels', None), point_cloud_range=model_info_dict['point_cloud_range'],
+            voxel_size=model_info_dict['voxel_size'], num_class=self.num_class if not self.model_cfg.ROI_HEAD.CLASS_AGNOSTIC else 1)
+        model_info_dict['module_list'].append(m)
+        return m, model_info_dict
+
     @staticmethod
     def generate_recall_record(box_preds, recall_dict, batch_index, data_dict=None, thresh_list=None):
         """Recall bookkeeping of the evaluation loop (reference detector3d_template.py:318-358): ground-truth boxes matched by
@@ -131,11 +141,16 @@ class Detector3DTemplate(nn.Module):
             raise NotImplementedError("MULTI_CLASSES_NMS: True (per-class NMS in post_processing) is not built")
         if isinstance(batch_dict['batch_cls_preds'], list) or isinstance(batch_dict['batch_box_preds'], list):
             raise NotImplementedError("list-valued batch_cls_preds / batch_box_preds (multi-head) are not built")
-        if batch_dict.get('has_class_labels', False):
-            raise NotImplementedError("has_class_labels (labels from a RoI head) is not built in post_processing")
+        nms_off = not nms.get('NMS', True)
+        if batch_dict.get('has_class_labels', False) and not nms_off:
+            raise NotImplementedError("has_class_labels (labels from a RoI head) with NMS on is not built in post_processing")
         if batch_dict.get('batch_index', None) is not None:
             raise NotImplementedError("batch_index (concatenated predictions) is not built in post_processing")
-        if not nms.get('NMS', True) or cfg.get('OUTPUT_RAW_SCORE', False) or nms.NMS_TYPE != 'nms_gpu':
+        if cfg.get('OUTPUT_RAW_SCORE', False):
+            raise NotImplementedError("post_processing: OUTPUT_RAW_SCORE True is not built")
+        if nms_off:
+            return self.post_processing_without_nms(batch_dict)
+        if nms.NMS_TYPE != 'nms_gpu':
             raise NotImplementedError("post_processing: only NMS_TYPE nms_gpu with OUTPUT_RAW_SCORE False is built")
         from gdmae_hip import lib as L
         cls_all, box_all = batch_dict['batch_cls_preds'], batch_dict['batch_box_preds']
@@ -170,6 +185,32 @@ class Detector3DTemplate(nn.Module):
             pred, recall_dict = self.finish_sample(box_preds[orig], scores, labels, recall_dict, b, batch_dict,
                                                    all_boxes=box_preds if 'rois' in batch_dict else None)
             pred_dicts.append(pred)
+        return pred_dicts, recall_dict
+
+    def post_processing_without_nms(self, batch_dict):
+        """The ``NMS: False`` branch (reference detector3d_template.py:269-299; the two-stage configs): the score is the maximum
+        over the classes, the label comes from ``roi_labels`` (``batch_pred_labels``) when ``has_class_labels`` and is the best
+        class + 1 otherwise, no box is selected; rows with label 0 (padded RoIs) are dropped; the recall record is computed on
+        all boxes when RoIs are present."""
+        cfg = self.model_cfg.POST_PROCESSING
+        cls_all, box_all = batch_dict['batch_cls_preds'], batch_dict['batch_box_preds']
+        assert box_all.dim() == 3 and cls_all.shape[2] in (1, self.num_class)
+        recall_dict, pred_dicts = {}, []
+        for b in range(batch_dict['batch_size']):
+            box_preds = box_all[b]
+            cp = cls_all[b] if batch_dict['cls_preds_normalized'] else torch.sigmoid(cls_all[b])
+            scores, labels = torch.max(cp, dim=-1)
+            if batch_dict.get('has_class_labels', False):
+                labels = batch_dict['roi_labels' if 'roi_labels' in batch_dict else 'batch_pred_labels'][b]
+            else:
+                labels = labels + 1
+            ok = labels != 0
+            final_boxes, final_scores, final_labels = box_preds[ok], scores[ok], labels[ok]
+            if cfg.get('RECALL_MODE', 'normal') == 'normal':
+                recall_dict = self.generate_recall_record(box_preds=final_boxes if 'rois' not in batch_dict else box_preds,
+                                                          recall_dict=recall_dict, batch_index=b, data_dict=batch_dict,
+                                                          thresh_list=cfg.RECALL_THRESH_LIST)
+            pred_dicts.append({'pred_boxes': final_boxes, 'pred_scores': final_scores, 'pred_labels': final_labels})
         return pred_dicts, recall_dict
 
     def finish_sample(self, boxes, scores, labels, recall_dict, batch_index, batch_dict, all_boxes=None):

@@ -924,6 +924,27 @@ int gdmae_adam_step_shadow(float* param, const float* grad, float* exp_avg, floa
                            int n_segments, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
                            float max_norm, float grad_scale, const float* sq_norm, void* param_bf16, void* stream);
 
+/* ---- RoI point pooling of the two-stage detector (csrc/roi_pool.hip; replaces the patch_ops extension:
+ * pcdet/ops/patch_ops/src/patch_query_gpu.cu, roipatch_dfvs_pool3d_gpu.cu, and the feature code of
+ * graphrcnn_head.py:201-244) ------------------------------------------------------------------- *
+ * points (n_points, n_cols = 1 + 3 + C) fp32 device [batch, x, y, z, features]; rois (batch, n_rois, roi_cols >= 7) fp32 device
+ * [x, y, z, dx, dy, dz, heading, ...]; range_xy HOST [x_min, y_min, x_max, y_max] (the point filter, bounds inclusive);
+ * patch_lo HOST [x, y] origin of the 1 m BEV patch grid of patches_x x patches_y patches (the head uses round(range -/+ 1));
+ * extra_width HOST [3] (POOL_EXTRA_WIDTH).  hash_size is accepted and unused.
+ * Outputs: pooled_idx (batch, n_rois, num_fps_points) int32 rows of `points`; pooled_num (batch, n_rois) int32;
+ * feats_local (batch n_rois, num_fps_points, 3 + C + 6) fp32 [canonical xyz, point features, local corners of the un-enlarged RoI];
+ * xyz_global (batch n_rois, num_fps_points, 3) fp32.  Deterministic: a voxel is represented by its lowest row, a RoI with more
+ * than num_dvs_points voxels keeps the lowest rows, FPS starts at the lowest row and resolves ties towards the lowest row, a patch
+ * covered by more than boxes_per_patch RoIs keeps the lowest RoI indices; an empty RoI gives zero rows.  Exact for any number of
+ * points and voxels per RoI.  phases: 1 = patch -> point lists and RoI spans into the workspace, 2 = pooling from a workspace that
+ * phase 1 filled for the same inputs, 3 = both.  No host synchronisation. */
+size_t gdmae_roi_dfvs_pool_workspace_bytes(long long n_points, int batch, int n_rois, int patches_x, int patches_y);
+int gdmae_roi_dfvs_pool(const float* points, long long n_points, int n_cols, const float* rois, int batch, int n_rois,
+                        int roi_cols, const float* range_xy, const float* patch_lo, int patches_x, int patches_y,
+                        const float* extra_width, int num_dvs_points, int num_fps_points, int hash_size, float lambda,
+                        float delta, int boxes_per_patch, int phases, int* pooled_idx, int* pooled_num, float* feats_local,
+                        float* xyz_global, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
