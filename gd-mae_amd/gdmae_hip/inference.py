@@ -1,9 +1,15 @@
-"""Inference engine of the fine-tuned detectors: DynVFE -> SPTBackbone -> SSTBEVBackbone, then CenterHead (``CenterPoint``) or
-AnchorHeadSingle (``PointPillar``, the shipped KITTI fine-tune config).
+"""Inference engine of the fine-tuned detectors: DynVFE -> SPTBackbone -> SSTBEVBackbone, then CenterHead (``CenterPoint``),
+AnchorHeadSingle (``PointPillar``, the shipped KITTI fine-tune config) or CenterHead + GraphRCNNHead (``GraphRCNN``, the shipped
+two-stage config).
 
-    engine = compile_detector(model)           # model: CenterPoint / PointPillar from build_network, .eval(), on the GPU
+    engine = compile_detector(model)           # model: CenterPoint / PointPillar / GraphRCNN from build_network, .eval(), on the GPU
     boxes, recall = engine(batch_dict)         # what model(batch_dict) returns in eval mode
-    maps = engine.head_maps(batch_dict)        # per-head prediction maps (+ .spatial_features_2d, ...)
+    maps = engine.head_maps(batch_dict)        # per-head prediction maps (+ .spatial_features_2d, ...) of the first stage
+    out = engine.refine(batch_dict)            # GraphRCNN only: the second stage on RoIs the caller supplies
+
+The two-stage variant runs the first stage as the CenterPoint engine does, pools the RoIs' points with ``gdmae_roi_dfvs_pool`` and
+runs the whole head behind the pooling - graph network, shared layer, heads, box decoding, score fusion - in the two launches of
+``gdmae_roi_graph_forward`` (csrc/roi_graph.hip); ``post_processing`` takes its ``NMS: False`` branch.
 
 The trunk (everything up to the channels-last bf16 BEV map) is shared; the head is a variant.  The anchor variant never writes the
 dense per-anchor arrays: ``gdmae_anchor_head_infer`` goes from the BEV map to the anchors at or above SCORE_THRESH (score, label,
@@ -228,19 +234,22 @@ class DetectorEngine:
     def _refresh_head(self, dev):
         raise NotImplementedError
 
+    def _check_stages(self, model):
+        if getattr(model, "roi_head", None) is not None or getattr(model, "point_head", None) is not None:
+            _no("two-stage heads")
+
     def __init__(self, model):
         from pcdet.models.backbones_3d.vfe.dyn_vfe import DynVFE
         from pcdet.models.backbones_3d.spt_backbone import SPTBackbone
         from pcdet.models.backbones_2d.sst_bev_backbone import SSTBEVBackbone
         if not next(model.parameters()).is_cuda:       # what is not covered first (NotImplementedError), then how it is called
-            _no("the model must be on the GPU (the CenterPoint / PointPillar engines run on the library's kernels only)")
+            _no("the model must be on the GPU (the CenterPoint / PointPillar / GraphRCNN engines run on the library's kernels only)")
         if model.training:
             raise ValueError("gdmae_hip.inference: compile_detector needs the model in evaluation mode (call model.eval() first)")
         for name, kind in (("vfe", DynVFE), ("backbone_3d", SPTBackbone), ("backbone_2d", SSTBEVBackbone), ("dense_head", self.HEAD())):
             if not isinstance(getattr(model, name, None), kind):
                 _no(f"model.{name} must be a {kind.__name__}")
-        if getattr(model, "roi_head", None) is not None or getattr(model, "point_head", None) is not None:
-            _no("two-stage heads")
+        self._check_stages(model)
         self.model = model
         self.refresh()
 
@@ -451,6 +460,149 @@ class CenterPointEngine(DetectorEngine):
             return m.post_processing(bd)
 
 
+ROI_GRAPH_CONFIG = {'IN_DIM': 11, 'MLPS': [32, 32, 64], 'CALIB_DIM': 64, 'EXP_MLPS': [512], 'OUT_DIM': 256, 'K': 8, 'USE_FEATS_DIS': False,
+                    'USE_REDUCTION': True, 'USE_SHORT_CUT': True}
+
+
+def fold_roi_head(head):
+    """The ``folded`` fp32 buffer of ``gdmae_roi_graph_pack`` (include/gdmae_hip.h) from a ``GraphRCNNHead`` in eval mode: every
+    BatchNorm folded in fp64 into the product in front of it, an edge layer split into P = a W_nbr and Q = a (W_ctr - W_nbr).
+    Anything the kernels are not specialised to is refused by name."""
+    from pcdet.models.roi_heads.graphrcnn_head import GraphRCNNHead
+    if not isinstance(head, GraphRCNNHead):
+        _no(f"model.roi_head must be a GraphRCNNHead, not {type(head).__name__}")
+    gnn_cfg, gnn = head.model_cfg.ATTN_GNN_CONFIG, head.attn_gnn_layer
+    for key, want in ROI_GRAPH_CONFIG.items():
+        got = gnn_cfg.get(key, None)
+        got = list(got) if isinstance(got, (list, tuple)) else got
+        if got != want:
+            _no(f"ROI_HEAD.ATTN_GNN_CONFIG.{key}: {got} (the second-stage kernels are specialised to {want})")
+    if gnn.reduction is None or gnn.shortcut is None:
+        _no("ROI_HEAD.ATTN_GNN_CONFIG.USE_REDUCTION / USE_SHORT_CUT: False (the second-stage kernels include both blocks)")
+    pool = head.roilocal_dfvs_pool3d_layer
+    if int(pool.num_fps_points) != 256 or int(head.model_cfg.DFVS_CONFIG.NUM_FPS_POINTS) != 256:
+        _no(f"ROI_HEAD.DFVS_CONFIG.NUM_FPS_POINTS: {pool.num_fps_points} (the second-stage kernels take 256 points per RoI)")
+    if head.num_class != 1:
+        _no(f"a RoI head with num_class = {head.num_class} (the second-stage kernels are class-agnostic: CLASS_AGNOSTIC True)")
+    if head.box_coder.code_size != 7:
+        _no("a RoI head box coder with other than 7 codes")
+    dev = head.cls_layers.weight.device
+
+    def conv(c, cout, cin, bias):
+        kind = nn.Conv2d if c.weight.dim() == 4 else nn.Conv1d
+        if not isinstance(c, kind) or tuple(c.weight.shape[:2]) != (cout, cin) or c.weight[0, 0].numel() != 1 or (c.bias is not None) != bias:
+            _no(f"second-stage layer {c} where a 1 x 1 convolution {cin} -> {cout} ({'with' if bias else 'no'} bias) is expected")
+        return c.weight.detach().double().reshape(cout, cin), (c.bias.detach().double() if bias else None)
+
+    out = []
+    if gnn.k != 8 or len(gnn.edge_layes) != 3:
+        _no("ROI_HEAD.ATTN_GNN_CONFIG: K / MLPS of the built graph network differ from the config")
+    cin = 11
+    for seq, c in zip(gnn.edge_layes, (32, 32, 64)):
+        cv, bn = _block(seq, nn.Conv2d)
+        w, _ = conv(cv, c, 2 * cin, False)
+        a, b = fold_bn(bn, c, dev)
+        out += [a[:, None] * w[:, :cin], a[:, None] * (w[:, cin:] - w[:, :cin]), b]
+        cin = c
+    cal = list(gnn.calib.children())
+    if len(cal) != 4 or not isinstance(cal[2], nn.ReLU):
+        _no("calib block other than Conv1d, BatchNorm1d, ReLU, Conv1d")
+    w, _ = conv(cal[0], 64, 128, False)
+    a, b = fold_bn(cal[1], 64, dev)
+    out += [a[:, None] * w, b, *conv(cal[3], 128, 64, True)]
+    for seq, co, ci in ((gnn.expansion, 512, 128), (gnn.reduction, 256, 512)):
+        cv, bn = _block(seq, nn.Conv1d)
+        w, _ = conv(cv, co, ci, False)
+        a, b = fold_bn(bn, co, dev)
+        out += [a[:, None] * w, b]
+    sc = gnn.shortcut
+    a, b = fold_bn(sc.norm1, 256, dev)
+    out += [2.0 * a, b, *conv(sc.conv1, 256, 256, True), *conv(sc.conv2, 256, 256, True), *fold_bn(sc.norm2, 256, dev)]      # x + dropout1(x) = 2 x
+    cv, bn = _block(head.shared_fc_layer, nn.Conv1d)
+    w, _ = conv(cv, 256, 256, False)
+    a, b = fold_bn(bn, 256, dev)
+    wc, bc = conv(head.cls_layers, 1, 256, True)
+    wr, br = conv(head.reg_layers, 7, 256, True)
+    out += [a[:, None] * w, b, torch.cat([wc, wr]), torch.cat([bc, br])]
+    flat = torch.cat([t.reshape(-1) for t in out]).float().contiguous()
+    if flat.numel() != L.load().gdmae_roi_graph_folded_floats():
+        _no("second-stage weights do not fill the kernel's folded buffer")
+    return flat
+
+
+class GraphRCNNEngine(CenterPointEngine):
+    """``GraphRCNN``: the CenterPoint engine's first stage, its boxes as RoIs, ``gdmae_roi_dfvs_pool``, and the head behind the pooling
+    in ``gdmae_roi_graph_forward`` (two launches, bf16 operands in the five wide products, fp32 elsewhere)."""
+
+    def _check_stages(self, model):
+        if getattr(model, "point_head", None) is not None:
+            _no("a model with a point_head")
+        if getattr(model, "roi_head", None) is None:
+            _no("a GraphRCNN without a roi_head")
+
+    def _refresh_head(self, dev):
+        super()._refresh_head(dev)
+        flat = fold_roi_head(self.model.roi_head)
+        self.roi_packed = torch.empty(L.load().gdmae_roi_graph_packed_bytes(), dtype=torch.uint8, device=dev)
+        L.call("gdmae_roi_graph_pack", L.ptr(flat), L.ptr(self.roi_packed), L.stream())
+
+    def _second_stage(self, points, B, rois, roi_scores, normalized):
+        head = self.model.roi_head
+        if not (points.is_cuda and rois.is_cuda and roi_scores.is_cuda):
+            _no("the second stage runs on device tensors only")
+        rois = rois.float().contiguous()
+        roi_scores = roi_scores.float().contiguous()
+        if rois.dim() != 3 or rois.shape[0] != B or rois.shape[2] < 7 or tuple(roi_scores.shape) != tuple(rois.shape[:2]):
+            _no(f"rois {tuple(rois.shape)} / roi_scores {tuple(roi_scores.shape)} (want (B, M, >= 7) and (B, M))")
+        M = rois.shape[1]
+        dev = rois.device
+        r = head.pc_range
+        _, num, feats, _ = head.roilocal_dfvs_pool3d_layer.pool(points, rois[..., :7].contiguous(), range_xy=[r[0], r[1], r[3], r[4]])
+        if feats.shape[1:] != (256, 11):
+            _no(f"pooled features {tuple(feats.shape[1:])} per RoI (the second-stage kernels take 256 points x 11 = 3 + 2 point features + 6)")
+        out = {'rcnn_cls': torch.empty(B * M, 1, dtype=torch.float32, device=dev), 'rcnn_reg': torch.empty(B * M, 7, dtype=torch.float32, device=dev),
+               'batch_cls_preds': torch.empty(B, M, 1, dtype=torch.float32, device=dev),
+               'batch_box_preds': torch.empty(B, M, 7, dtype=torch.float32, device=dev), 'pooled_num': num.view(-1)}
+        if B * M:
+            ws = torch.empty(L.load().gdmae_roi_graph_workspace_bytes(B * M), dtype=torch.uint8, device=dev)
+            L.call("gdmae_roi_graph_forward", L.ptr(feats), L.ptr(num), L.ptr(rois), rois.shape[2], L.ptr(roi_scores), B, M, int(bool(normalized)),
+                   L.ptr(self.roi_packed), L.ptr(out['rcnn_cls']), L.ptr(out['rcnn_reg']), L.ptr(out['batch_box_preds']),
+                   L.ptr(out['batch_cls_preds']), None, L.ptr(ws), ws.numel(), L.stream())
+        return out
+
+    @torch.no_grad()
+    def refine(self, batch_dict):
+        """The second stage on the caller's RoIs: ``points``, ``batch_size``, ``rois`` (B, M, >= 7), ``roi_scores`` (B, M)
+        (probabilities when ``cls_preds_normalized``, logits otherwise), ``roi_labels`` -> rcnn_cls (B M, 1), rcnn_reg (B M, 7),
+        batch_cls_preds (B, M, 1), batch_box_preds (B, M, 7), pooled_num (B M).  Rows of padded RoIs (label 0) are computed like any
+        other and dropped by ``post_processing``."""
+        self._check_fresh()
+        with torch.autocast("cuda", enabled=False):
+            return self._second_stage(batch_dict['points'], int(batch_dict['batch_size']), batch_dict['rois'], batch_dict['roi_scores'],
+                                      batch_dict.get('cls_preds_normalized', False))
+
+    @torch.no_grad()
+    def proposals(self, batch_dict):
+        """The first stage's RoIs as ``CenterHead.forward`` leaves them: rois (B, M, 7), roi_scores, roi_labels (zero-padded)."""
+        maps = self.head_maps(batch_dict)
+        B = int(batch_dict['batch_size'])
+        hd = self.model.dense_head
+        with torch.autocast("cuda", enabled=False):
+            rois, scores, labels = hd.reorder_rois_for_refining(B, hd.generate_predicted_boxes(B, maps))
+        return {'batch_size': B, 'rois': rois, 'roi_scores': scores, 'roi_labels': labels, 'has_class_labels': True,
+                'cls_preds_normalized': True}
+
+    @torch.no_grad()
+    def __call__(self, batch_dict):
+        bd = self.proposals(batch_dict)
+        with torch.autocast("cuda", enabled=False):
+            out = self._second_stage(batch_dict['points'], bd['batch_size'], bd['rois'], bd['roi_scores'], True)
+            bd['batch_cls_preds'], bd['batch_box_preds'] = out['batch_cls_preds'], out['batch_box_preds']
+            if 'gt_boxes' in batch_dict:
+                bd['gt_boxes'] = batch_dict['gt_boxes']
+            return self.model.post_processing(bd)
+
+
 class AnchorEngine(DetectorEngine):
     """``PointPillar`` with ``AnchorHeadSingle``: the three 1 x 1 convolutions, the score threshold and the box decoding of the
     survivors are ``gdmae_anchor_head_infer`` (two launches); the tail of ``post_processing`` runs on the survivors."""
@@ -550,12 +702,15 @@ class AnchorEngine(DetectorEngine):
 
 
 def compile_detector(model) -> DetectorEngine:
-    """Fold and pack ``model`` (a CenterPoint or PointPillar from ``pcdet.models.build_network``, in eval mode, on the GPU) for
-    inference."""
+    """Fold and pack ``model`` (a CenterPoint, PointPillar or GraphRCNN from ``pcdet.models.build_network``, in eval mode, on the
+    GPU) for inference."""
     from pcdet.models.detectors.centerpoint import CenterPoint
+    from pcdet.models.detectors.graph_rcnn import GraphRCNN
     from pcdet.models.detectors.pointpillar import PointPillar
     if isinstance(model, CenterPoint):
         return CenterPointEngine(model)
     if isinstance(model, PointPillar):
         return AnchorEngine(model)
-    _no(f"compile_detector covers the CenterPoint and PointPillar detectors, not {type(model).__name__}")
+    if isinstance(model, GraphRCNN):
+        return GraphRCNNEngine(model)
+    _no(f"compile_detector covers the CenterPoint, PointPillar and GraphRCNN detectors, not {type(model).__name__}")

@@ -945,6 +945,35 @@ int gdmae_roi_dfvs_pool(const float* points, long long n_points, int n_cols, con
                         float delta, int boxes_per_patch, int phases, int* pooled_idx, int* pooled_num, float* feats_local,
                         float* xyz_global, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- second stage after the pooling (csrc/roi_graph.hip; GraphRCNNHead in eval mode: graphrcnn_head.py:60-130, 246-302 and
+ * roi_head_template.py:226-254), specialised to ATTN_GNN_CONFIG IN_DIM 11, MLPS [32, 32, 64], CALIB_DIM 64, EXP_MLPS [512],
+ * OUT_DIM 256, K 8, USE_REDUCTION, USE_SHORT_CUT, 256 points per RoI, one class, 7 box codes ------------------- *
+ * folded: gdmae_roi_graph_folded_floats() fp32 device values, every BatchNorm already folded (a into the rows of the product in
+ * front of it, b into the bias), matrices [out][in] row-major, in this order:
+ *   edge layer 1: P (32, 11) = a W_nbr, Q (32, 11) = a (W_ctr - W_nbr), b (32); edge layer 2: P (32, 32), Q (32, 32), b (32);
+ *   edge layer 3: P (64, 32), Q (64, 32), b (64); calib: W1 (64, 128), b1 (64), W2 (128, 64), bias2 (128);
+ *   expansion W (512, 128), b (512); reduction W (256, 512), b (256); norm1 a (256) TIMES 2 (x + dropout1(x) in eval), b (256);
+ *   shortcut conv1 W (256, 256), b (256); conv2 W (256, 256), b (256); norm2 a (256), b (256); shared layer W (256, 256), b (256);
+ *   heads W (8, 256): the class row, then the 7 box rows; b (8).
+ * gdmae_roi_graph_pack writes the image (gdmae_roi_graph_packed_bytes() bytes): the weights of edge layers 2 / 3, calib and the
+ * expansion rounded once to bf16 (nearest even) in matrix-core operand order, the rest in fp32.
+ * gdmae_roi_graph_forward: feats_local (batch n_rois, 256, 11) fp32 and pooled_num (batch n_rois) int32 as gdmae_roi_dfvs_pool
+ * writes them; rois (batch, n_rois, roi_cols >= 7) fp32; roi_scores (batch, n_rois) fp32, probabilities when scores_normalized,
+ * logits otherwise.  Outputs: rcnn_cls (batch n_rois, 1), rcnn_reg (batch n_rois, 7), batch_box_preds (batch, n_rois, 7) decoded,
+ * batch_cls_preds (batch, n_rois, 1) = sqrt(sigmoid(rcnn_cls)) sqrt(roi score).  A RoI with pooled_num 0 reads all-zero inputs.
+ * Neighbours: the 8 slots with the smallest fp32 (dx dx + dy dy) + dz dz, the slot itself included, ties to the lowest slot.
+ * nbr_debug: NULL, or (batch n_rois, 256, 8) int32 receiving the neighbour slots used (nearest first).  workspace:
+ * gdmae_roi_graph_workspace_bytes(batch n_rois) bytes (512 fp32 per RoI between the two launches).  Deterministic, every RoI's
+ * result depends on its own rows only.  No host synchronisation. */
+size_t gdmae_roi_graph_folded_floats(void);
+size_t gdmae_roi_graph_packed_bytes(void);
+size_t gdmae_roi_graph_workspace_bytes(long long n_rois_total);
+int gdmae_roi_graph_pack(const float* folded, void* packed, void* stream);
+int gdmae_roi_graph_forward(const float* feats_local, const int* pooled_num, const float* rois, int roi_cols,
+                            const float* roi_scores, int batch, int n_rois, int scores_normalized, const void* packed,
+                            float* rcnn_cls, float* rcnn_reg, float* batch_box_preds, float* batch_cls_preds, int* nbr_debug,
+                            void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
