@@ -9,6 +9,7 @@
 // k_ch_draw rasterises one box per workgroup with an atomic max on the (non-negative) float bit patterns - a maximum is
 // order independent, so the heat map is deterministic.
 #include "common.h"
+#include "center_decode.h"
 
 struct ChBox {
   int cx, cy, r, cls;     // integer centre (feature-map cells), Gaussian radius, class index inside the head (0-based) / -1
@@ -161,43 +162,26 @@ extern "C" int gdmae_center_head_targets_iou(const float* gt_boxes, int B, int n
 struct ChDecode {
   const long long* cell;     // (B, K)
   const float* score;        // (B, K) sigmoid heat-map value
-  const float *center, *center_z, *dim, *rot, *vel, *iou;   // (B, 2 | 1 | 3 | 2 | 2 | 1, H, W); vel / iou optional
-  int B, K, H, W;
-  float x0, y0, vsx, vsy, stride;
-  float lim[6];
-  float score_thresh;
-  int use_thresh;
+  ChMaps M;
+  ChGeom G;
+  int B, K;
   int box_dim;               // 7, or 9 with vel
   float* boxes;              // (B, K, box_dim)
   int* labels;               // (B, K) class index inside the head
   float* ious;               // (B, K) clamp((iou + 1) / 2, 0, 1), or 1 without an iou map
   unsigned char* valid;      // (B, K) inside the post-centre range and above the score threshold
 };
+// the arithmetic is ch_decode_cell (center_decode.h), shared with the batched tail of center_detect.hip
 __global__ __launch_bounds__(256) void k_ch_decode(ChDecode D) {
   const long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
   if (i >= (long long)D.B * D.K) return;
   const int b = (int)(i / D.K);
-  const long long hw = (long long)D.H * D.W;
-  const long long c = D.cell[i];
-  const int cls = (int)(c / hw);
-  const long long site = c % hw;
-  const int y = (int)(site / D.W), x = (int)(site % D.W);
-  auto at = [&](const float* m, int ch, int k) { return m[((long long)b * ch + k) * hw + site]; };
-  float box[9];
-  box[0] = (((float)x + at(D.center, 2, 0)) * D.stride) * D.vsx + D.x0;
-  box[1] = (((float)y + at(D.center, 2, 1)) * D.stride) * D.vsy + D.y0;
-  box[2] = at(D.center_z, 1, 0);
-  box[3] = expf(at(D.dim, 3, 0)); box[4] = expf(at(D.dim, 3, 1)); box[5] = expf(at(D.dim, 3, 2));
-  box[6] = atan2f(at(D.rot, 2, 1), at(D.rot, 2, 0));                 // rot = [cos, sin]
-  if (D.vel) { box[7] = at(D.vel, 2, 0); box[8] = at(D.vel, 2, 1); }
+  float box[9], q;
+  int cls;
+  const bool ok = ch_decode_cell(D.M, D.G, b, D.cell[i], D.score[i], box, cls, q);
   for (int e = 0; e < D.box_dim; ++e) D.boxes[i * D.box_dim + e] = box[e];
   D.labels[i] = cls;
-  float q = 1.f;
-  if (D.iou) q = fminf(fmaxf((at(D.iou, 1, 0) + 1.f) * 0.5f, 0.f), 1.f);
   D.ious[i] = q;
-  bool ok = true;
-  for (int e = 0; e < 3; ++e) ok = ok && box[e] >= D.lim[e] && box[e] <= D.lim[3 + e];
-  if (D.use_thresh) ok = ok && D.score[i] > D.score_thresh;
   D.valid[i] = ok ? 1 : 0;
 }
 extern "C" int gdmae_center_head_decode(const long long* cell, const float* score, const float* center, const float* center_z,
@@ -207,11 +191,10 @@ extern "C" int gdmae_center_head_decode(const long long* cell, const float* scor
                                         int use_score_thresh, float* boxes, int* labels, float* ious, unsigned char* valid, void* stream) {
   GD_REQUIRE(B >= 1 && K >= 1 && H >= 1 && W >= 1, "center_head_decode: bad sizes");
   ChDecode D;
-  D.cell = cell; D.score = score; D.center = center; D.center_z = center_z; D.dim = dim; D.rot = rot; D.vel = vel; D.iou = iou;
-  D.B = B; D.K = K; D.H = H; D.W = W;
-  D.x0 = pc_range[0]; D.y0 = pc_range[1]; D.vsx = voxel_size[0]; D.vsy = voxel_size[1]; D.stride = feature_map_stride;
-  for (int e = 0; e < 6; ++e) D.lim[e] = post_center_limit_range[e];
-  D.score_thresh = score_thresh; D.use_thresh = use_score_thresh; D.box_dim = vel ? 9 : 7;
+  D.cell = cell; D.score = score;
+  D.M = ChMaps{center, center_z, dim, rot, vel, iou};
+  ch_fill_geom(D.G, H, W, pc_range, voxel_size, feature_map_stride, post_center_limit_range, score_thresh, use_score_thresh);
+  D.B = B; D.K = K; D.box_dim = vel ? 9 : 7;
   D.boxes = boxes; D.labels = labels; D.ious = ious; D.valid = valid;
   hipLaunchKernelGGL(k_ch_decode, dim3(gd_div_up((long long)B * K, 256)), dim3(256), 0, (hipStream_t)stream, D);
   GD_LAUNCH_CHECK();

@@ -459,6 +459,16 @@ class CenterPointEngine(DetectorEngine):
                 bd['gt_boxes'] = batch_dict['gt_boxes']
             return m.post_processing(bd)
 
+    @torch.no_grad()
+    def detect(self, batch_dict):
+        """``head_maps``, then the batched tail (``CenterHead.generate_predicted_boxes_batched``: three launches for all samples and
+        classes): pred_boxes (B, n, 7 | 9), pred_scores (B, n), pred_labels (B, n) int64, num (B) int32 on the device, rows at or beyond
+        num[b] zero; n depends on the config only.  Nothing is read on the host after the trunk and no recall record is computed;
+        ``CenterHead.padded_to_pred_dicts`` gives the per-sample list of ``engine(batch_dict)``."""
+        maps = self.head_maps(batch_dict)
+        with torch.autocast("cuda", enabled=False):
+            return self.model.dense_head.generate_predicted_boxes_batched(int(batch_dict['batch_size']), maps)
+
 
 ROI_GRAPH_CONFIG = {'IN_DIM': 11, 'MLPS': [32, 32, 64], 'CALIB_DIM': 64, 'EXP_MLPS': [512], 'OUT_DIM': 256, 'K': 8, 'USE_FEATS_DIS': False,
                     'USE_REDUCTION': True, 'USE_SHORT_CUT': True}
@@ -601,6 +611,25 @@ class GraphRCNNEngine(CenterPointEngine):
             if 'gt_boxes' in batch_dict:
                 bd['gt_boxes'] = batch_dict['gt_boxes']
             return self.model.post_processing(bd)
+
+    @torch.no_grad()
+    def detect(self, batch_dict):
+        """Both stages on padded device tensors: the first stage through the batched tail, its padded output as the RoIs, then the
+        second stage.  ONE host read in between, ``num.max()``: the RoI rows are trimmed to M = max(1, largest count of the batch), the M
+        of ``proposals()``, so the second stage runs as many rows as ``engine(batch_dict)`` does and no more.  -> pred_boxes (B, M, 7),
+        pred_scores (B, M), pred_labels (B, M) int64 (the RoI labels; 0 in padded rows, whose boxes and scores are zero), num (B).
+        No recall record."""
+        B = int(batch_dict['batch_size'])
+        first = super().detect(batch_dict)
+        M = max(1, int(first['num'].max()))                       # the host read
+        with torch.autocast("cuda", enabled=False):
+            rois = first['pred_boxes'][:, :M].contiguous()
+            labels = first['pred_labels'][:, :M].contiguous()
+            out = self._second_stage(batch_dict['points'], B, rois, first['pred_scores'][:, :M].contiguous(), True)
+            real = labels != 0
+            boxes, scores = out['batch_box_preds'], out['batch_cls_preds'].max(dim=-1)[0]
+            return {'pred_boxes': torch.where(real.unsqueeze(-1), boxes, torch.zeros_like(boxes)),
+                    'pred_scores': torch.where(real, scores, torch.zeros_like(scores)), 'pred_labels': labels, 'num': first['num']}
 
 
 class AnchorEngine(DetectorEngine):

@@ -181,6 +181,8 @@ SIGNATURES = {
     "gdmae_focal_loss_fwd": (_I, [_P, _I, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
     "gdmae_focal_loss_bwd": (_I, [_P, _I, _P, _P, _I, _I, _I, _I, _P, _P, _P, _I, _P]),
     "gdmae_center_head_decode": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _F, _P, _F, _I, _P, _P, _P, _P, _P]),
+    "gdmae_center_head_detect_workspace_bytes": (_Z, [_I, _I, _I]),
+    "gdmae_center_head_detect": (_I, [_P] * 8 + [_I] * 4 + [_P, _P, _F, _P, _F, _I, _I, _P, _P, _P, _P, _P, _I, _I] + [_P] * 6),
     "gdmae_anchor_targets_workspace_bytes": (_Z, [_I, _I, _I]),
     "gdmae_anchor_targets": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _F, _I, _P, _P, _P, _P, _P, _P, _P]),
     "gdmae_anchor_loss_rows": (_I, []),

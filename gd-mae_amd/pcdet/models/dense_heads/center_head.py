@@ -296,6 +296,94 @@ class CenterHead(nn.Module):
                 per_sample[b][0].append(bx[keep]), per_sample[b][1].append(sc[keep]), per_sample[b][2].append(lab[keep] + 1)
         return [{'pred_boxes': torch.cat(p[0]), 'pred_scores': torch.cat(p[1]), 'pred_labels': torch.cat(p[2])} for p in per_sample]
 
+    # ---- the same tail for the whole batch on the device (csrc/center_detect.hip)
+    def _batched_plan(self):
+        """Host-side constants of ``generate_predicted_boxes_batched``: (K, class_aware, per-class lists indexed by the GLOBAL class,
+        to_global, n_out).  Everything the batched tail does not build is refused here by name."""
+        cfg = self.model_cfg.POST_PROCESSING
+        nms = cfg.NMS_CONFIG
+        if len(self.class_names_each_head) != 1:
+            raise NotImplementedError(f"generate_predicted_boxes_batched: {len(self.class_names_each_head)} heads "
+                                      "(CLASS_NAMES_EACH_HEAD with several entries; the batched tail serves one head)")
+        if nms.NMS_TYPE not in ('nms_gpu', 'multi_class_nms'):
+            raise NotImplementedError(f"generate_predicted_boxes_batched: NMS_TYPE {nms.NMS_TYPE} (built: nms_gpu, multi_class_nms)")
+        K = int(cfg.MAX_OBJ_PER_SAMPLE)
+        if K > 1024:
+            raise NotImplementedError(f"generate_predicted_boxes_batched: MAX_OBJ_PER_SAMPLE {K} > 1024 (the candidates of a sample are "
+                                      "sorted in LDS)")
+        names = self.class_names_each_head[0]
+        C = len(names)
+        if C > 8:
+            raise NotImplementedError(f"generate_predicted_boxes_batched: {C} classes in one head (at most 8)")
+        to_global = [self.class_names.index(c) for c in names]
+        if nms.NMS_TYPE == 'nms_gpu':
+            aware = 0
+            thresh, pre, post, rect = [float(nms.NMS_THRESH)], [int(nms.NMS_PRE_MAXSIZE)], [int(nms.NMS_POST_MAXSIZE)], [0.0]
+        else:
+            aware = 1
+            n = len(nms.NMS_THRESH)                       # the op-by-op loop visits the classes 0 .. n - 1 only
+            thresh = [float(nms.NMS_THRESH[c]) if c < n else 0.0 for c in range(C)]
+            pre = [int(nms.NMS_PRE_MAXSIZE[c]) if c < n else 0 for c in range(C)]
+            post = [int(nms.NMS_POST_MAXSIZE[c]) if c < n else 0 for c in range(C)]
+            rect = [float(r) for r in nms.IOU_RECTIFIER][:C]
+            if len(rect) < C:
+                raise NotImplementedError("generate_predicted_boxes_batched: IOU_RECTIFIER shorter than the class list")
+        pad = lambda v, z: v + [z] * (8 - len(v))   # noqa: E731
+        return K, aware, pad(thresh, 0.0), pad(pre, 0), pad(post, 0), pad(rect, 0.0), to_global, C
+
+    def batched_rows(self, num_cells=None):
+        """Rows per sample of the padded output: min(K, sum of NMS_POST_MAXSIZE), K = min(MAX_OBJ_PER_SAMPLE, cells of the heat map)."""
+        K, aware, _, _, post, _, _, C = self._batched_plan()
+        if num_cells is not None:
+            K = min(K, int(num_cells))
+        return max(1, min(K, sum(min(p, K) for p in (post[:C] if aware else post[:1]))))
+
+    def generate_predicted_boxes_batched(self, batch_size, pred_dicts):
+        """``generate_predicted_boxes`` for all samples and classes in ``gdmae_center_head_detect`` (three launches behind the sigmoid
+        and the top-K, no host read): -> {'pred_boxes' (B, n, 7 | 9), 'pred_scores' (B, n), 'pred_labels' (B, n) int64, 'num' (B) int32}
+        on the device, n = ``batched_rows()``; rows at or beyond num[b] are zero (label 0, the padding of
+        ``reorder_rois_for_refining``).  ``padded_to_pred_dicts`` turns it into the per-sample list."""
+        K, aware, thresh, pre, post, rect, to_global, C = self._batched_plan()
+        cfg = self.model_cfg.POST_PROCESSING
+        if len(pred_dicts) != 1:
+            raise NotImplementedError(f"generate_predicted_boxes_batched: {len(pred_dicts)} prediction dicts for one head")
+        pd = pred_dicts[0]
+        if not all(v.is_cuda for v in pd.values()):
+            raise NotImplementedError("generate_predicted_boxes_batched: CPU tensors (the tail runs in libgdmae_hip.so, no CPU fallback)")
+        hm = pd['hm'].float().sigmoid()
+        B, Ch, H, W = hm.shape
+        if Ch != C or B != int(batch_size):
+            raise NotImplementedError(f"generate_predicted_boxes_batched: heat map {tuple(hm.shape)} for batch_size {batch_size}, {C} classes")
+        dev = hm.device
+        f = lambda name: pd[name].float().contiguous()   # noqa: E731
+        vel = f('vel') if 'vel' in self.separate_head_cfg.HEAD_ORDER else None
+        iou = f('iou') if 'iou' in pd else None
+        k = min(K, C * H * W)
+        n_out = self.batched_rows(C * H * W)
+        score, cell = torch.topk(hm.reshape(B, -1), k)
+        bd = 9 if vel is not None else 7
+        out = {'pred_boxes': torch.empty(B, n_out, bd, dtype=torch.float32, device=dev),
+               'pred_scores': torch.empty(B, n_out, dtype=torch.float32, device=dev),
+               'pred_labels': torch.empty(B, n_out, dtype=torch.int64, device=dev),
+               'num': torch.empty(B, dtype=torch.int32, device=dev)}
+        ws = torch.empty(L.load().gdmae_center_head_detect_workspace_bytes(B, k, bd), dtype=torch.uint8, device=dev)
+        L.call("gdmae_center_head_detect", L.ptr(cell.contiguous()), L.ptr(score.contiguous()), L.ptr(f('center')), L.ptr(f('center_z')),
+               L.ptr(f('dim')), L.ptr(f('rot')), L.ptr(vel), L.ptr(iou), B, k, H, W,
+               L.host_f32([self.point_cloud_range[0], self.point_cloud_range[1]]), L.host_f32([self.voxel_size[0], self.voxel_size[1]]),
+               float(self.feature_map_stride), L.host_f32(list(cfg.POST_CENTER_LIMIT_RANGE)),
+               float(cfg.SCORE_THRESH if cfg.SCORE_THRESH is not None else 0.0), int(cfg.SCORE_THRESH is not None),
+               C, L.host_f32(thresh), L.host_i32(pre), L.host_i32(post), L.host_f32(rect), L.host_i32(to_global), aware, n_out,
+               L.ptr(out['pred_boxes']), L.ptr(out['pred_scores']), L.ptr(out['pred_labels']), L.ptr(out['num']), L.ptr(ws), L.stream())
+        return out
+
+    @staticmethod
+    def padded_to_pred_dicts(out):
+        """The padded tensors of ``generate_predicted_boxes_batched`` -> the per-sample list ``generate_predicted_boxes`` returns.
+        ONE host read (``num``)."""
+        num = out['num'].tolist()
+        return [{'pred_boxes': out['pred_boxes'][b, :n], 'pred_scores': out['pred_scores'][b, :n], 'pred_labels': out['pred_labels'][b, :n]}
+                for b, n in enumerate(num)]
+
     @staticmethod
     def _nms_one(boxes, scores, thresh, pre_max, post_max):
         """Indices (descending score) surviving the rotated NMS of the ``pre_max`` best boxes, at most ``post_max`` of them."""

@@ -848,6 +848,23 @@ int gdmae_center_head_decode(const long long* cell, const float* score, const fl
                              const float* pc_range /* host [x0, y0] */, const float* voxel_size /* host [vx, vy] */,
                              float feature_map_stride, const float* post_center_limit_range /* host [6] */, float score_thresh,
                              int use_score_thresh, float* boxes, int* labels, float* ious, unsigned char* valid, void* stream);
+/* The whole evaluation tail of ONE CenterHead head for all samples in three launches, nothing read on the host (csrc/center_detect.hip;
+ * it reproduces CenterHead.generate_predicted_boxes sample by sample: decode as gdmae_center_head_decode, score rectification, sort,
+ * NMS_PRE_MAXSIZE, rotated NMS with the bev_iou of gdmae_nms_bev, NMS_POST_MAXSIZE).  cell / score (B, K <= 1024) as torch.topk over the
+ * sigmoid heat map leaves them (cell in [0, C H W), score >= 0), maps and geometry as gdmae_center_head_decode.  HOST arrays per GLOBAL
+ * class (C <= 8 entries each): thresh (>= 0), pre_max, post_max, rectifier; to_global (C): class inside the head -> 0-based global
+ * class, a permutation.  class_aware 1 = multi_class_nms: r = powf(s, 1 - a_c) powf(q, a_c) (a_c = 0: r = s bit for bit), one NMS per
+ * class, output class by class in descending r; 0 = nms_gpu: r = s, one NMS over all classes with the values of slot 0.  Ties in r go
+ * to the lower top-K position.  n_out = min(K, sum of the post_max in use).  Outputs fully written: boxes (B, n_out, 7 | 9), scores
+ * (B, n_out), labels (B, n_out) int64 1-based global, count (B) int32; rows at or beyond count[b] are zero (label 0).  A sample's rows
+ * depend on that sample only.  Errors: K > 1024, C > 8, a negative threshold, a wrong n_out. */
+size_t gdmae_center_head_detect_workspace_bytes(int B, int K, int box_dim);
+int gdmae_center_head_detect(const long long* cell, const float* score, const float* center, const float* center_z, const float* dim,
+                             const float* rot, const float* vel, const float* iou, int B, int K, int H, int W, const float* pc_range,
+                             const float* voxel_size, float feature_map_stride, const float* post_center_limit_range, float score_thresh,
+                             int use_score_thresh, int C, const float* thresh, const int* pre_max, const int* post_max,
+                             const float* rectifier, const int* to_global, int class_aware, int n_out, float* boxes, float* scores,
+                             long long* labels, int* count, void* workspace, void* stream);
 
 /* ---- f4 (next row): rotated BEV IoU and NMS for evaluation ------------------------------------------ *
  * Replace the iou3d_nms CUDA extension (pcdet/ops/iou3d_nms/src/iou3d_nms_kernel.cu:236-414; iou3d_nms.cpp): boxes

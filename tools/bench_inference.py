@@ -2,12 +2,18 @@
 evaluation path (model.eval() under bf16 autocast - and in fp32 with --fp32 - and torch.no_grad()), same process, same seeded
 synthetic KITTI-shape frames, the paths alternating, warm-up excluded, events around the timed loop and one sync after it.
 
-    python tools/bench_inference.py [--config D|kitti] [--batches 1 8] [--runs 5] [--calls 10] [--warmup 3] [--path both|engine|parent]
+    python tools/bench_inference.py [--config D|kitti|ts] [--batches 1 8] [--runs 5] [--calls 10] [--warmup 3]
+                                    [--path both|engine|parent|detect]
 
 --config D: the CenterPoint detector of config D (0.16 m pillars).  --config kitti: the PointPillar / AnchorHeadSingle detector of
 the shipped KITTI fine-tune config (configs.kitti_finetune_cfg(), 0.32 m pillars), conv_cls.bias set so that the scores straddle
 SCORE_THRESH; this run also times the head alone on the engine's bf16 BEV map: gdmae_anchor_head_infer (two launches) against the
 row product on the library GEMM + gdmae_anchor_decode + gdmae_anchor_select.
+
+--config ts: the two-stage GraphRCNN detector of configs.waymo_two_stage_cfg() (Waymo-shape grid and cloud, CenterHead with
+multi_class_nms over three classes, then the RoI head); it has engine paths only.  --path detect: ``engine.detect`` (the batched
+CenterHead tail) against ``engine(batch_dict)`` (the op-by-op tail: what the engine call has been since the engines were
+added), alternating; then the two tails alone on the same head maps, with their launch counts.
 
 Prints every run pair, the medians, frames/s, the kernel-launch count of one engine call and of one parent call (torch profiler,
 device activity), and the bytes of the encoder's backward-only side outputs one engine call writes.  --path engine | parent runs one
@@ -87,23 +93,59 @@ def head_alone(eng, net, pts, B, args):
     print(f"batch {B} head alone: new {a:.3f} ms, parent (gemm + decode + select) {b:.3f} ms, new / parent = {a / b:.3f}", flush=True)
 
 
+def tails_alone(eng, net, pts, B, args):
+    """The CenterHead tail alone on the engine's head maps: generate_predicted_boxes (op-by-op: per sample and class a mask gather, a
+    sort, a two-launch NMS and a host read) against generate_predicted_boxes_batched (sigmoid, top-K and three launches)."""
+    hd = net.dense_head
+    maps = eng.head_maps({"points": pts, "batch_size": B})
+
+    def old():
+        with torch.no_grad(), torch.autocast("cuda", enabled=False):
+            return hd.generate_predicted_boxes(B, maps)
+
+    def new():
+        with torch.no_grad(), torch.autocast("cuda", enabled=False):
+            return hd.generate_predicted_boxes_batched(B, maps)
+    for fn in (new, old):
+        for _ in range(args.warmup):
+            fn()
+    torch.cuda.synchronize()
+    print(f"batch {B} tail alone: boxes per sample, batched {new()['num'].tolist()}  op-by-op {[int(d['pred_boxes'].shape[0]) for d in old()]}",
+          flush=True)
+    res = {"new": [], "old": []}
+    for r in range(args.runs):
+        res["new"].append(timed(new, args.calls))
+        res["old"].append(timed(old, args.calls))
+        print(f"batch {B} tail run {r}: batched {res['new'][-1]:.3f} ms  op-by-op {res['old'][-1]:.3f} ms", flush=True)
+    a, b = statistics.median(res["new"]), statistics.median(res["old"])
+    print(f"batch {B} tail alone: batched {a:.3f} ms ({launches(new)} launches), op-by-op {b:.3f} ms ({launches(old)} launches), "
+          f"batched / op-by-op = {a / b:.3f}", flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--config", default="D", choices=["D", "kitti"])
+    ap.add_argument("--config", default="D", choices=["D", "kitti", "ts"])
     ap.add_argument("--fp32", action="store_true", help="also time the parent's fp32 evaluation path")
     ap.add_argument("--batches", type=int, nargs="+", default=[8, 1])
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--calls", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--path", default="both", choices=["both", "engine", "parent"])
+    ap.add_argument("--path", default="both", choices=["both", "engine", "parent", "detect"])
     ap.add_argument("--no-launch-count", action="store_true", help="skip the in-process tracer (when an external kernel trace runs)")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     if args.config == "kitti":
         cfg, ds = configs.kitti_finetune_cfg()
         skw = dict(beams=32, azimuths=600, extra=800, features=4)
+    elif args.config == "ts":
+        cfg, ds = configs.waymo_two_stage_cfg()
+        skw = dict(beams=64, azimuths=2650, extra=10400, features=5)
+        if args.path != "detect":
+            ap.error("--config ts has engine paths only: use --path detect")
     else:
         cfg, ds, skw = configs.named_config("D")
+    if args.path == "detect" and args.config == "kitti":
+        ap.error("--path detect: the anchor-head engine has its own fused tail")
     torch.manual_seed(3)
     net = build_network(cfg, len(ds.class_names), ds, logging.getLogger("bench")).to(dev).eval()
     g = torch.Generator().manual_seed(5)
@@ -128,8 +170,12 @@ def main():
         def parent_fp32():
             with torch.no_grad():
                 return net({"points": pts, "batch_size": B})
+        def detect():
+            return eng.detect({"points": pts, "batch_size": B})
         paths = [("engine", engine), ("parent", parent)]
-        if args.path != "both":
+        if args.path == "detect":
+            paths = [("detect", detect), ("engine", engine)]
+        elif args.path != "both":
             paths = [p for p in paths if p[0] == args.path]
         if args.fp32 and args.path != "engine":
             paths.append(("parent_fp32", parent_fp32))
@@ -150,6 +196,10 @@ def main():
                 print(f"batch {B}: engine / {other} median = {statistics.median(res['engine']) / statistics.median(res[other]):.3f}", flush=True)
         if args.config == "kitti" and args.path == "both":
             head_alone(eng, net, pts, B, args)
+        if args.path == "detect":
+            print(f"batch {B}: detect / engine median = {statistics.median(res['detect']) / statistics.median(res['engine']):.3f}", flush=True)
+            tails_alone(eng, net, pts, B, args)
+            continue
         if args.path != "parent" and not args.no_launch_count:
             maps = eng.head_maps({"points": pts, "batch_size": B})
             # backward-only side outputs of gdmae_encoder_stage_fwd (gdmae_encoder_layer_bytes: the `saved` block per layer)
