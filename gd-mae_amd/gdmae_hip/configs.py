@@ -163,6 +163,19 @@ def optimization_cfg(batch_size_per_gpu=8, num_epochs=30):
                      'LR_WARMUP': False, 'WARMUP_EPOCH': 1, 'GRAD_NORM_CLIP': 10})
 
 
+def waymo_finetune_data_cfg():
+    """(DATA_AUGMENTOR.AUG_CONFIG_LIST, DATA_PROCESSOR) of the Waymo fine-tune config (waymo_models/gd_mae.yaml:18-68), as plain
+    dicts with the yaml's keys: what ``input_pipeline.GpuFinetuneInputPipeline`` is built from."""
+    import copy
+
+    from .input_pipeline import FINETUNE_AUG_CONFIG
+    aug = copy.deepcopy(list(FINETUNE_AUG_CONFIG))
+    proc = [{'NAME': 'mask_points_and_boxes_outside_range', 'REMOVE_OUTSIDE_BOXES': True},
+            {'NAME': 'shuffle_points', 'SHUFFLE_ENABLED': {'train': True, 'test': False}},
+            {'NAME': 'calculate_grid_size', 'VOXEL_SIZE': [0.32, 0.32, 6.0]}]
+    return aug, proc
+
+
 class SyntheticDatasetInfo:
     """The attributes ``Detector3DTemplate.build_networks`` reads from the dataset object
     (detector3d_template.py:45-53; dataset.py:27-41; data_processor.py:166-171)."""

@@ -124,3 +124,321 @@ class GpuInputPipeline:
         else:
             return pts
         return pts.index_select(0, idx)             # rows are 4 * (1 + F) = 20-24 bytes: below the 16-byte row kernels
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Fine-tune mode: gt_sampling + the world augmentation of points AND boxes + range masks + collate
+#
+#     gt_sampling -> random_world_flip -> random_world_rotation -> random_world_scaling -> heading limit_period
+#       -> class selection + class column -> mask_points_and_boxes_outside_range -> shuffle_points -> collate_batch
+#
+# (database_sampler.py, data_augmentor.py, dataset.py:125-162 / :181-192, data_processor.py:77-90).  The host draws what
+# the reference draws, with the same np.random calls in the same order (per frame: the candidates of every sample
+# group, then the world parameters); the two launches of csrc/gt_sampling.hip do the rest.
+# ---------------------------------------------------------------------------------------------------------------------
+# tools/cfgs/waymo_models/gd_mae.yaml:18-55
+FINETUNE_AUG_CONFIG = ({"NAME": "gt_sampling", "BACKEND": {"NAME": "HardDiskBackend"}, "USE_ROAD_PLANE": False,
+        "DB_INFO_PATH": ["waymo_processed_data_waymo_dbinfos_train_sampled_1.pkl"], "USE_SHARED_MEMORY": False,
+        "DB_DATA_PATH": ["waymo_processed_data_gt_database_train_sampled_1_global.npy"],
+        "PREPARE": {"filter_by_min_points": ["Vehicle:5", "Pedestrian:10", "Cyclist:10"], "filter_by_difficulty": [-1]},
+        "SAMPLE_GROUPS": ["Vehicle:15", "Pedestrian:10", "Cyclist:10"], "NUM_POINT_FEATURES": 5, "REMOVE_POINTS": True,
+        "REMOVE_EXTRA_WIDTH": [0.0, 0.0, 0.0], "LIMIT_WHOLE_SCENE": True},
+       {"NAME": "random_world_flip", "PROBABILITY": 0.5, "ALONG_AXIS_LIST": ["x", "y"]},
+       {"NAME": "random_world_rotation", "PROBABILITY": 1.0, "WORLD_ROT_ANGLE": [-0.78539816, 0.78539816]},
+       {"NAME": "random_world_scaling", "PROBABILITY": 1.0, "WORLD_SCALE_RANGE": [0.95, 1.05]})
+
+MAX_CANDIDATES = 64         # per frame (csrc/gt_sampling.hip: GS_MAX_CAND; the library also refuses more than 448 GT boxes)
+
+
+class GtDatabase:
+    """The GT database of ``gt_sampling`` in its ``*_global.npy`` form: ``points`` (N, F) float32 holds every object's
+    LOCAL points (box centre subtracted, not rotated) back to back, ``offsets`` (M, 2) the row range of every entry,
+    ``boxes`` (M, 7) its ``box3d_lidar``, ``names`` (M) its class.  ``class_index[name]`` lists the entries of a class
+    in file order: the list the reference's sampler indexes (``db_infos[name]``)."""
+
+    def __init__(self, points, offsets, boxes, names, num_points_in_gt=None, difficulty=None):
+        if offsets is None:
+            raise NotImplementedError("database without global offsets: only the *_global.npy form (global_data_offset) is supported")
+        self.points = np.ascontiguousarray(points, dtype=np.float32)
+        self.offsets = np.asarray(offsets, dtype=np.int64).reshape(-1, 2)
+        boxes = np.asarray(boxes)
+        if boxes.ndim == 2 and boxes.shape[1] > 7:
+            raise NotImplementedError("GT boxes with more than 7 columns (velocities) are not supported")
+        self.boxes = boxes.reshape(-1, 7).astype(np.float32)
+        self.names = np.asarray(names).astype(str).reshape(-1)
+        M = self.offsets.shape[0]
+        assert self.points.ndim == 2 and self.boxes.shape[0] == M and self.names.shape[0] == M
+        assert M == 0 or (self.offsets.min() >= 0 and self.offsets.max() <= self.points.shape[0] and (self.offsets[:, 0] <= self.offsets[:, 1]).all())
+        self.num_points_in_gt = None if num_points_in_gt is None else np.asarray(num_points_in_gt, dtype=np.int64).reshape(-1)
+        self.difficulty = None if difficulty is None else np.asarray(difficulty, dtype=np.int64).reshape(-1)
+        self.class_index = {}
+        for n in dict.fromkeys(self.names.tolist()):
+            self.class_index[n] = np.flatnonzero(self.names == n)
+        self.points_dev = None
+
+    @classmethod
+    def from_reference_files(cls, info_pkl_paths, global_npy_path):
+        """The reference's ``*_dbinfos_*.pkl`` ({class: [info, ...]}; several files extend every class's list, as
+        database_sampler.py:31-34 does) and its ``*_gt_database_*_global.npy``."""
+        import pickle
+        per_class = {}
+        for path in ([info_pkl_paths] if isinstance(info_pkl_paths, (str, bytes)) or hasattr(info_pkl_paths, "__fspath__") else info_pkl_paths):
+            with open(path, "rb") as f:
+                for name, infos in pickle.load(f).items():
+                    per_class.setdefault(name, []).extend(infos)
+        infos = [i for lst in per_class.values() for i in lst]
+        if any("global_data_offset" not in i for i in infos):
+            raise NotImplementedError("database without global offsets: an info has no global_data_offset")
+        return cls(np.load(global_npy_path), [i["global_data_offset"] for i in infos] or np.zeros((0, 2)),
+                   np.stack([np.asarray(i["box3d_lidar"]) for i in infos]) if infos else np.zeros((0, 7)),
+                   [i["name"] for i in infos], [i.get("num_points_in_gt", -1) for i in infos], [i.get("difficulty", 0) for i in infos])
+
+    def _select(self, keep):
+        pick = lambda a: None if a is None else a[keep]      # noqa: E731
+        db = GtDatabase(self.points, self.offsets[keep], self.boxes[keep], self.names[keep], pick(self.num_points_in_gt), pick(self.difficulty))
+        db.points_dev = self.points_dev
+        return db
+
+    def prepare(self, prepare_cfg):
+        """``PREPARE`` of the sampler config, in its key order (database_sampler.py:36-37, :93-120)."""
+        db = self
+        for func, val in dict(prepare_cfg or {}).items():
+            if func == "filter_by_min_points":
+                if db.num_points_in_gt is None:
+                    raise ValueError("filter_by_min_points needs the database's num_points_in_gt")
+                keep = np.ones(db.names.shape[0], bool)
+                for name_num in val:
+                    name, num = name_num.split(":")
+                    if int(num) > 0:
+                        keep &= ~((db.names == name) & (db.num_points_in_gt < int(num)))
+            elif func == "filter_by_difficulty":
+                if db.difficulty is None:
+                    raise ValueError("filter_by_difficulty needs the database's difficulty")
+                keep = ~np.isin(db.difficulty, np.asarray(list(val), dtype=np.int64))
+            else:
+                raise NotImplementedError(f"PREPARE step {func}")
+            db = db._select(keep)
+        return db
+
+    def to(self, device):
+        """Resident mode: the object points live on the device, a batch copies none of them."""
+        self.points_dev = torch.from_numpy(self.points).to(device)
+        return self
+
+
+def check_sampler_cfg(cfg):
+    """Refuses, by name, what the fine-tune pass does not restate."""
+    if cfg.get("USE_ROAD_PLANE", False):
+        raise NotImplementedError("gt_sampling USE_ROAD_PLANE: True")
+    if cfg.get("DATABASE_WITH_FAKELIDAR", False):
+        raise NotImplementedError("gt_sampling DATABASE_WITH_FAKELIDAR")
+    if cfg.get("FADE_EPOCH", 0) != 0:
+        raise NotImplementedError("gt_sampling FADE_EPOCH != 0")
+
+
+def sampler_state(sampler_cfg, database, class_names):
+    """Pointer and permutation of every sample group (database_sampler.py:41-54): the pointer starts past the end, so
+    the first draw of a class permutes."""
+    check_sampler_cfg(sampler_cfg)
+    groups = []
+    for x in sampler_cfg["SAMPLE_GROUPS"]:
+        name, num = x.split(":")
+        if name not in class_names:
+            continue
+        n = int(database.class_index.get(name, np.zeros(0)).shape[0]) if isinstance(database, GtDatabase) else int(database[name])
+        groups.append({"name": name, "sample_num": int(num), "pointer": n, "indices": np.arange(n), "size": n})
+    return {"groups": groups, "limit_whole_scene": bool(sampler_cfg.get("LIMIT_WHOLE_SCENE", False))}
+
+
+def draw_candidates(state, gt_names):
+    """Candidate draw of ONE frame, group by group in SAMPLE_GROUPS order, consuming ``np.random`` like
+    DataBaseSampler.__call__ / sample_with_fixed_number (database_sampler.py:122-139, :230-235): -> [(class name,
+    indices into that class's list)].  LIMIT_WHOLE_SCENE subtracts the frame's own count of the name, over ALL names."""
+    names = np.asarray(gt_names).astype(str)
+    out = []
+    for g in state["groups"]:
+        num = g["sample_num"] - int(np.sum(g["name"] == names)) if state["limit_whole_scene"] else g["sample_num"]
+        if num <= 0:
+            continue
+        if g["pointer"] >= g["size"]:
+            g["indices"] = np.random.permutation(g["size"])
+            g["pointer"] = 0
+        out.append((g["name"], np.asarray(g["indices"][g["pointer"]:g["pointer"] + num], dtype=np.int64)))
+        g["pointer"] += num
+    return out
+
+
+def finetune_params_table(params: Sequence[dict]) -> np.ndarray:
+    """``params_table`` plus, in column 5, the angle rounded to fp32: what ``gt_boxes[:, 6] += noise_rotation`` adds to a
+    float32 heading (data_augmentor.py:108)."""
+    t = params_table(params)
+    t[:, 5] = [np.float32(p["angle"]) for p in params]
+    return t
+
+
+class GpuFinetuneInputPipeline(GpuInputPipeline):
+    def __init__(self, point_cloud_range, class_names, aug_config: Optional[Sequence[dict]] = FINETUNE_AUG_CONFIG, database: Optional[GtDatabase] = None,
+                 shuffle: bool = True, resident: bool = True, min_num_corners: int = 1, device: Optional[torch.device] = None):
+        aug_config = list(aug_config or [])
+        world = [c for c in aug_config if c["NAME"] != "gt_sampling"]
+        for c in world:
+            if c["NAME"] not in ("random_world_flip", "random_world_rotation", "random_world_scaling"):
+                raise NotImplementedError(f"augmentation {c['NAME']} is outside the fine-tune input pipeline")
+        super().__init__(point_cloud_range, world, shuffle, device)
+        self.range6 = [float(v) for v in point_cloud_range]
+        self.class_names = list(class_names)
+        self.min_num_corners = int(min_num_corners)
+        sampler = [c for c in aug_config if c["NAME"] == "gt_sampling"]
+        if len(sampler) > 1 or (sampler and aug_config[0]["NAME"] != "gt_sampling"):
+            raise NotImplementedError("gt_sampling must be the first and only sampler of the augmentation list")
+        self.sampler_cfg = sampler[0] if sampler and database is not None else None
+        self.database = self.state = None
+        self.resident = bool(resident)
+        self.extra_width, self.remove_points = [0.0, 0.0, 0.0], True
+        self.time_kernels, self.kernel_events = False, None       # tools/bench_finetune_input.py: events around the two launches
+        if sampler:
+            check_sampler_cfg(sampler[0])
+        if self.sampler_cfg is not None:
+            self.database = database.prepare(self.sampler_cfg.get("PREPARE", {}))
+            self.state = sampler_state(self.sampler_cfg, self.database, self.class_names)
+            self.group_of = {g["name"]: k for k, g in enumerate(self.state["groups"])}
+            self.remove_points = bool(self.sampler_cfg.get("REMOVE_POINTS", True))
+            self.extra_width = [float(v) for v in self.sampler_cfg.get("REMOVE_EXTRA_WIDTH", [0.0, 0.0, 0.0])]
+            if self.resident and self.database.points_dev is None:
+                self.database.to(self.device)
+
+    def __call__(self, frames: List[np.ndarray], gt_boxes: List[np.ndarray], gt_names: List[Sequence[str]],
+                 params: Optional[Sequence[dict]] = None, candidates: Optional[Sequence[Sequence]] = None,
+                 perms: Optional[Sequence[np.ndarray]] = None) -> dict:
+        """frames: B raw clouds (n_i, F) float32; gt_boxes: B arrays (m_i, 7); gt_names: B name lists (ALL of the frame's
+        names, also those outside ``class_names``).  -> {'points' (N, 1 + F), 'gt_boxes' (B, max_gt, 8), 'batch_size',
+        'num_gt' (host list: kept boxes per frame; 0 is where the reference re-draws another sample), 'sampled_valid'
+        (per frame, one flag per candidate)}.  ``params`` / ``candidates`` (per frame [(class name, indices into the
+        class's list), ...] in group order) / ``perms``: explicit decisions for parity tests."""
+        B = len(frames)
+        F = int(frames[0].shape[1])
+        db = self.database
+        drawn_c, drawn_p = [], []
+        ident = {"flip_x": False, "flip_y": False, "angle": 0.0, "scale": 1.0}
+        for b in range(B):                                  # the reference's order: per frame, the sampler, then the world draws
+            if candidates is not None:
+                drawn_c.append(list(candidates[b]))
+            else:
+                drawn_c.append(draw_candidates(self.state, gt_names[b]) if self.state is not None else [])
+            if params is None:
+                drawn_p.append(draw_world_params(self.aug_config) if self.aug_config else dict(ident))
+        params = drawn_p if params is None else params
+        if any(len(c) for c in drawn_c) and db is None:
+            raise ValueError("candidates without a database")
+        if db is not None and db.points.shape[1] != F:
+            raise ValueError(f"database points have {db.points.shape[1]} columns, the frames {F}")
+
+        # ---- host tables -------------------------------------------------------------------------------------------
+        box_rows, desc, cand_group, cand_entry, cap = [], [], [], [], 0
+        for b in range(B):
+            gb = np.asarray(gt_boxes[b])
+            if gb.ndim == 2 and gb.shape[1] > 7:
+                raise NotImplementedError("GT boxes with more than 7 columns (velocities) are not supported")
+            gb = gb.reshape(-1, 7).astype(np.float32)
+            names = np.asarray(gt_names[b]).astype(str).reshape(-1)
+            assert names.shape[0] == gb.shape[0], "one name per GT box"
+            cls = np.array([self.class_names.index(n) + 1 if n in self.class_names else 0 for n in names], np.float32)
+            ents, grp = [], []
+            for name, local in drawn_c[b]:
+                e = db.class_index[name][np.asarray(local, dtype=np.int64)]
+                ents.append(e)
+                grp += [self.group_of[name]] * len(e)
+            ents = np.concatenate(ents) if ents else np.zeros(0, np.int64)
+            ccls = np.array([self.class_names.index(n) + 1 for n in db.names[ents]], np.float32) if len(ents) else np.zeros(0, np.float32)
+            cb = db.boxes[ents] if len(ents) else np.zeros((0, 7), np.float32)
+            desc.append((sum(r.shape[0] for r in box_rows), gb.shape[0], len(ents), len(cand_group)))
+            box_rows.append(np.concatenate([np.concatenate([gb, cb]), np.concatenate([cls, ccls])[:, None]], 1))
+            cand_group += grp
+            cand_entry.append(ents)
+            cap = max(cap, int((cls > 0).sum()) + len(ents))
+        C = len(cand_group)
+        n_groups = len(self.state["groups"]) if self.state is not None else 0
+        boxes_h = np.concatenate(box_rows).astype(np.float32) if box_rows else np.zeros((0, 8), np.float32)
+        desc_h = np.asarray(desc, np.int32).reshape(B, 4)
+
+        # virtual rows: per frame the object points of every candidate, then the scene points
+        n_scene = sum(f.shape[0] for f in frames)
+        n_obj = sum(int(db.offsets[e, 1] - db.offsets[e, 0]) for ents in cand_entry for e in ents)
+        staged_rows = n_scene + (0 if self.resident else n_obj)
+        host = self._staging(max(staged_rows, 1) * F).view(-1, F)[:max(staged_rows, 1)]
+        hv = host.numpy()
+        seg, row, src, stage = [], 0, 0, n_scene
+        for b, f in enumerate(frames):
+            assert f.dtype == np.float32 and f.shape[1] == F
+            first = 1
+            for k, e in enumerate(cand_entry[b]):
+                s0, s1 = (int(v) for v in db.offsets[e])
+                if s1 > s0:
+                    if self.resident:
+                        seg.append((row, s0, 1, b, desc[b][0] + desc[b][1] + k, desc[b][3] + k, first, 0))
+                    else:
+                        hv[stage:stage + s1 - s0] = db.points[s0:s1]
+                        seg.append((row, stage, 0, b, desc[b][0] + desc[b][1] + k, desc[b][3] + k, first, 0))
+                        stage += s1 - s0
+                    row += s1 - s0
+                    first = 0
+            if f.shape[0]:
+                hv[src:src + f.shape[0]] = f
+                seg.append((row, src, 0, b, -1, -1, first, 0))
+                row += f.shape[0]
+                src += f.shape[0]
+        n_rows, S = row, len(seg)
+        assert n_rows < 2 ** 31
+        ints_h = np.concatenate([desc_h.reshape(-1), np.asarray(cand_group, np.int32), np.asarray(seg, np.int32).reshape(-1)]).astype(np.int32)
+        flts_h = np.concatenate([finetune_params_table(params).reshape(-1), boxes_h.reshape(-1)]).astype(np.float32)
+
+        # ---- device ------------------------------------------------------------------------------------------------
+        dev = self.device
+        raw = host.to(dev, non_blocking=True)
+        self._copied = torch.cuda.Event()
+        self._copied.record()
+        ints_d = torch.from_numpy(ints_h).to(dev)
+        flts_d = torch.from_numpy(flts_h).to(dev)
+        desc_d, group_d, seg_d = ints_d[:B * 4], ints_d[B * 4:B * 4 + C], ints_d[B * 4 + C:]
+        tab_d, boxes_d = flts_d[:B * 8], flts_d[B * 8:]
+        meta = torch.empty(3 * B + 1 + C, dtype=torch.int32, device=dev)      # [kept_off (B + 1) | num_gt (B) | n_valid (B) | valid (C)]
+        kept, num_gt_d, n_valid_d, valid_d = meta[:B + 1], meta[B + 1:2 * B + 1], meta[2 * B + 1:3 * B + 1], meta[3 * B + 1:]
+        rm_boxes = torch.empty(B, MAX_CANDIDATES, 8, dtype=torch.float32, device=dev)
+        gt_out = torch.empty(B, cap, 8, dtype=torch.float32, device=dev)
+        out = torch.empty(max(n_rows, 1), 1 + F, dtype=torch.float32, device=dev)
+        ws = torch.empty(L.load().gdmae_gt_sample_workspace_bytes(n_rows), dtype=torch.uint8, device=dev)
+        dptr = lambda t: t.data_ptr() if t.numel() else None      # noqa: E731  (views of the packed tables; empty ones are never read)
+        ev = self.kernel_events = [torch.cuda.Event(enable_timing=True) for _ in range(3)] if self.time_kernels else None
+        if ev:
+            ev[0].record()
+        try:
+            L.call("gdmae_gt_sample_select", dptr(boxes_d), desc_h.ctypes.data, dptr(desc_d), dptr(group_d), B, n_groups, dptr(tab_d),
+                   L.host_f32(self.range6), L.host_f32(self.extra_width), self.min_num_corners, cap, dptr(valid_d), L.ptr(rm_boxes),
+                   dptr(n_valid_d), dptr(gt_out), dptr(num_gt_d), L.stream())
+        except L.GdmaeHipError as e:
+            if "more than" in str(e):
+                raise NotImplementedError(str(e)) from e
+            raise
+        if ev:
+            ev[1].record()
+        db_d = db.points_dev if (db is not None and self.resident) else raw
+        L.call("gdmae_gt_sample_collate", L.ptr(raw), L.ptr(db_d), F, dptr(seg_d), S, n_rows, B, dptr(tab_d), dptr(boxes_d), dptr(valid_d),
+               L.ptr(rm_boxes), dptr(n_valid_d) if self.remove_points else None, L.host_f32(self.xy_range), L.ptr(out), dptr(kept), L.ptr(ws),
+               L.stream())
+        if ev:
+            ev[2].record()
+        meta_h = meta.tolist()                              # the one host read of the call: point counts and box counts together
+        kept_h, num_gt = meta_h[:B + 1], meta_h[B + 1:2 * B + 1]
+        valid_h = np.asarray(meta_h[3 * B + 1:], dtype=bool)
+        n = kept_h[B]
+        for b in range(B - 1, -1, -1):
+            if kept_h[b] < 0:
+                kept_h[b] = kept_h[b + 1]
+        pts = out[:n]
+        if perms is not None:
+            idx = torch.cat([torch.from_numpy(np.asarray(p, np.int64)) + kept_h[b] for b, p in enumerate(perms)]).to(dev)
+            pts = pts.index_select(0, idx)
+        elif self.shuffle and n > 0:
+            pts = pts.index_select(0, torch.argsort(pts[:, 0] + torch.rand(n, device=dev)))
+        return {"points": pts, "gt_boxes": gt_out[:, :max(num_gt) if num_gt else 0].contiguous(), "batch_size": B, "num_gt": num_gt,
+                "sampled_valid": [valid_h[d[3]:d[3] + d[2]] for d in desc]}

@@ -745,6 +745,34 @@ size_t gdmae_augment_collate_workspace_bytes(long long n_raw);
 int gdmae_augment_collate(const float* raw, long long n_raw, int F, const int* frame_off, int B, const float* frame_params,
                           const float* xy_range /* host */, float* out, int* kept_off, void* workspace, void* stream);
 
+/* ---- fine-tune mode of the input pipeline: GT sampling, boxes through the world augmentation -- *
+ * gdmae_gt_sample_select, one workgroup per frame: which database candidates a frame takes (database_sampler.py:242-251 with
+ *   bev_overlap of csrc/bev_iou.h), and the frame's row of the collated gt_boxes.
+ *   boxes (n_boxes, 8) fp32 device: per frame its GT boxes (ALL names) and then its candidates, columns
+ *     [x, y, z, dx, dy, dz, heading, class index + 1 (0: name outside class_names)];
+ *   frame_desc (B, 4) int32 = [first box row, GT boxes, candidates, first candidate] per frame, the same table on the host
+ *     (checked here: at most 64 candidates and 448 GT boxes per frame, else -1 is returned) and on the device;
+ *   cand_group (n_candidates) int32 device: sample group of every candidate, groups are processed in ascending order;
+ *   frame_params (B, 8) fp32 device = [flip_x, flip_y, cos, sin, scale, angle, 0, 0]; range host (6); extra_width host (3).
+ *   valid (n_candidates) int32; rm_boxes (B, 64, 8) fp32: the frame's valid candidates in order, enlarged, as
+ *     [cx, cy, cz, dx/2 + 1e-2, dy/2 + 1e-2, dz/2, cos(-heading), sin(-heading)]; n_valid (B) int32;
+ *   gt_boxes (B, cap, 8) fp32: GT boxes of the selected classes, then the valid candidates, transformed, those with at least
+ *     min_corners corners inside the closed range, zero rows behind them; num_gt (B) int32.
+ * gdmae_gt_sample_collate: paste, remove, world transformation, xy range mask and collate of the points as one compaction scan
+ *   over the virtual rows [frame 0: object points of every candidate, scene points; frame 1: ...].
+ *   seg (S, 8) int32 device, ascending first rows: [first virtual row, source row, source buffer (0 raw, 1 db), frame,
+ *     box row of the candidate or -1 for scene points, candidate, 1 on the frame's first segment, 0];
+ *   out (n_rows, 1 + F); kept_off (B + 1) int32: first output row per frame (-1: no virtual rows), kept_off[B] = rows written. */
+size_t gdmae_gt_sample_workspace_bytes(long long n_rows);
+int gdmae_gt_sample_select(const float* boxes, const int* frame_desc_host, const int* frame_desc, const int* cand_group, int B,
+                           int n_groups, const float* frame_params, const float* range /* host */,
+                           const float* extra_width /* host */, int min_corners, int cap, int* valid, float* rm_boxes,
+                           int* n_valid, float* gt_boxes, int* num_gt, void* stream);
+int gdmae_gt_sample_collate(const float* raw, const float* db, int F, const int* seg, int S, long long n_rows, int B,
+                            const float* frame_params, const float* boxes, const int* valid, const float* rm_boxes,
+                            const int* n_valid, const float* xy_range /* host */, float* out, int* kept_off, void* workspace,
+                            void* stream);
+
 /* ---- the reference's own native op API for this path, for arbitrary group ids ------------------- *
  * Drop-in equivalents of pybind module pcdet.ops.sst_ops.sst_ops_cuda (pcdet/ops/sst_ops/src/sst_ops_api.cpp:6-9):
  *   int ingroup_inds_wrapper(at::Tensor group_inds, at::Tensor out_inds)          (sst_ops.cpp:21-33)
