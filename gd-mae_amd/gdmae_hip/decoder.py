@@ -44,6 +44,9 @@ from . import timing
 # conv_out backward of the tile path: "implicit" = tile-compact output gradient + implicit-GEMM input gradient + gathered grouped
 # weight gradient (no tap matrix, no library GEMM); "taps" = the round-2 schedule (gdmae_conv3x3_grad_taps + two library GEMMs)
 CONV_BWD = os.environ.get("GDMAE_DEC_BWD", "implicit")
+# stages with an upsampling stride of 2 / 4 in the "implicit" backward: "1" = the weight gradient on token blocks (csrc/decoder_blocks.hip:
+# each token's dY halo staged once, the Zd rows never written), "0" = the rulebook path for every stage (A/B runs)
+BLOCK_BWD = os.environ.get("GDMAE_DEC_BLOCK", "1")
 
 BN_EPS, BN_MOM = 1e-3, 0.01
 
@@ -311,14 +314,25 @@ class DecoderHead(torch.autograd.Function):
                 # dZ rows of the stage's active sites: implicit GEMM over the rulebook (9 gathered dY rows per site)
                 dX = torch.empty(n, w, dtype=cdt, device=dev)
                 L.call("gdmae_spconv", L.ptr(dYc), 0, L.ptr(nbr), packed.data_ptr() + i * 9 * w * C2 * 2, n, C2, w, L.ptr(dX), 8, L.stream())
-                n_pad = int(L.load().gdmae_tap_dw_rows(n, w, C2))
-                Zd = torch.empty(n_pad, w, dtype=cdt, device=dev)
                 bg = bgz[col:col + w]
-                L.call("gdmae_rows_affine_relu_sub", L.ptr(P), _bf(P), None, n, w, L.ptr(ab), L.ptr(ab[w:]), L.ptr(bg), L.ptr(Zd),
-                       _bf(Zd), w, 0, L.stream())
-                # weight gradient: dWk[k][co][col + ci] += sum_t dY[site_t - k][co] * Zd[t][ci], nine taps in one grouped launch
-                ws = torch.empty(L.load().gdmae_tap_dw_workspace_bytes(n, w, C2), dtype=torch.uint8, device=dev)
-                L.call("gdmae_tap_dw", L.ptr(Zd), n, n_pad, w, L.ptr(dYc), L.ptr(nbr), C2, L.ptr(dWk), Cin, col, L.ptr(ws), L.stream())
+                u = int(ctx.geom[6][2][i])
+                ws_block = 0
+                if BLOCK_BWD != "0" and u in (2, 4) and P.dtype == torch.bfloat16 and P.is_contiguous() and sites[i].numel() >= n:
+                    ws_block = int(L.load().gdmae_decoder_block_dw_workspace_bytes(n, u))      # 0: more tokens per slice than it serves
+                if ws_block > 0:
+                    # weight gradient on token blocks: the same sums (bit for bit) with the halo of a token's u x u sites read once per
+                    # channel quarter; Zd stays in LDS
+                    ws = torch.empty(ws_block, dtype=torch.uint8, device=dev)
+                    L.call("gdmae_decoder_block_dw", L.ptr(P), L.ptr(ab), L.ptr(ab[w:]), L.ptr(bg), L.ptr(sites[i]), n, u, L.ptr(dYc),
+                           L.ptr(tile_slot), H, W, L.ptr(dWk), Cin, col, L.ptr(ws), L.stream())
+                else:
+                    n_pad = int(L.load().gdmae_tap_dw_rows(n, w, C2))
+                    Zd = torch.empty(n_pad, w, dtype=cdt, device=dev)
+                    L.call("gdmae_rows_affine_relu_sub", L.ptr(P), _bf(P), None, n, w, L.ptr(ab), L.ptr(ab[w:]), L.ptr(bg), L.ptr(Zd),
+                           _bf(Zd), w, 0, L.stream())
+                    # weight gradient: dWk[k][co][col + ci] += sum_t dY[site_t - k][co] * Zd[t][ci], nine taps in one grouped launch
+                    ws = torch.empty(L.load().gdmae_tap_dw_workspace_bytes(n, w, C2), dtype=torch.uint8, device=dev)
+                    L.call("gdmae_tap_dw", L.ptr(Zd), n, n_pad, w, L.ptr(dYc), L.ptr(nbr), C2, L.ptr(dWk), Cin, col, L.ptr(ws), L.stream())
             else:
                 G = torch.empty(n, 9 * C2, dtype=cdt, device=dev)
                 with timing.kernel("k_conv_grad_taps", 2.0 * n * 9 * C2 * G.element_size()):

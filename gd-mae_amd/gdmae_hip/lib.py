@@ -136,6 +136,8 @@ SIGNATURES = {
     "gdmae_tap_dw_rows": (_L, [_L, _I, _I]),
     "gdmae_tap_dw_workspace_bytes": (_Z, [_L, _I, _I]),
     "gdmae_tap_dw": (_I, [_P, _L, _L, _I, _P, _P, _I, _P, _I, _I, _P, _P]),
+    "gdmae_decoder_block_dw_workspace_bytes": (_Z, [_L, _I]),
+    "gdmae_decoder_block_dw": (_I, [_P, _P, _P, _P, _P, _L, _I, _P, _P, _I, _I, _P, _I, _I, _P, _P]),
     "gdmae_conv_block_fwd": (_I, [_P, _P]),
     "gdmae_conv_block_bwd": (_I, [_P, _P]),
     "gdmae_encoder_layer_bytes": (_I, [_L, _I, _I, _I, _I, _P, _P, _P]),

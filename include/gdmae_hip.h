@@ -524,6 +524,17 @@ long long gdmae_tap_dw_rows(long long n, int M, int N);      /* n_pad: rows G mu
 size_t gdmae_tap_dw_workspace_bytes(long long n, int M, int N);
 int gdmae_tap_dw(const void* G, long long n, long long n_pad, int M, const void* X, const int* nbr, int N, float* out, int ld_out,
                  int m_off, void* workspace, void* stream);
+/* ---- conv_out backward on token blocks (csrc/decoder_blocks.hip): source stages whose rows are the u x u sites of their tokens, token
+ *   after token (u = 2 / 4, 128 channels, bf16 rows; site[t u^2] = the first full-resolution cell of token t) ----
+ * gdmae_decoder_block_dw: out[k][co][m_off + ci] += sum_t dYc[site_t - offset(k)][co] * bf16(bf16(relu(a P[t] + b)) - bg)[ci] for the
+ *   9 taps (out (9, 128, ld_out) fp32; a, b (128) fp32, bg (128) bf16): the result of gdmae_rows_affine_relu_sub + gdmae_tap_dw over the
+ *   stage's rulebook - the same slices, chunk order and reduction, so the same bits - with each token's dY halo read once per channel
+ *   quarter and the Zd rows never written.  Partial tiles in `workspace` (gdmae_decoder_block_dw_workspace_bytes(n, u); 0 = this row
+ *   count / u is not served, use the rulebook path).  n = sites (rows of P). */
+size_t gdmae_decoder_block_dw_workspace_bytes(long long n, int u);
+int gdmae_decoder_block_dw(const void* P, const float* a, const float* b, const void* bg, const int* site, long long n, int u,
+                           const void* dYc, const int* tile_slot, int H, int W, float* out, int ld_out, int m_off, void* workspace,
+                           void* stream);
 int gdmae_conv_block_fwd(const gdmae_conv_block_args* args /* host */, void* stream);
 int gdmae_conv_block_bwd(const gdmae_conv_block_args* args /* host */, void* stream);
 
