@@ -15,6 +15,16 @@ from . import lib as L
 from . import ops
 
 
+def running_stats(bn):
+    """(running_mean, running_var, num_batches_tracked, momentum) that a training-mode forward of the nn.BatchNorm module ``bn`` updates;
+    (None, None, None, 0.0) when there is nothing to update (no module, eval mode, track_running_stats off)."""
+    if bn is None or not bn.training or bn.running_mean is None:
+        return None, None, None, 0.0
+    rm, rv, nb = bn.running_mean, bn.running_var, bn.num_batches_tracked
+    assert rm.dtype == torch.float32 and rv.dtype == torch.float32 and nb.dtype == torch.int64
+    return rm, rv, nb, float(bn.momentum)
+
+
 def fold(x2d: torch.Tensor, count: int, gamma: torch.Tensor, beta: torch.Tensor, eps: float, bn=None, partials=None):
     """Column statistics of the contiguous (R, C) fp32/bf16 matrix over ``count`` samples.
     -> (stats f64[2C] = mean|rstd, ab f32[2C] = a|b with y = a*x + b, mv f32[2C] = mean|biased var).
@@ -35,11 +45,7 @@ def fold(x2d: torch.Tensor, count: int, gamma: torch.Tensor, beta: torch.Tensor,
     ab = torch.empty(2 * C, dtype=torch.float32, device=dev)
     mv = torch.empty(2 * C, dtype=torch.float32, device=dev)
     ws = torch.empty(L.load().gdmae_colstats_workspace_bytes(C), dtype=torch.uint8, device=dev)
-    rm = rv = nb = None
-    mom = 0.0
-    if bn is not None and bn.training and bn.running_mean is not None:
-        rm, rv, nb, mom = bn.running_mean, bn.running_var, bn.num_batches_tracked, float(bn.momentum)
-        assert rm.dtype == torch.float32 and rv.dtype == torch.float32 and nb.dtype == torch.int64
+    rm, rv, nb, mom = running_stats(bn)
     if partials is not None:
         assert partials.dtype == torch.float32 and partials.is_contiguous() and partials.shape[1:] == (2, C), partials.shape
         L.call("gdmae_bn_fold_partials", L.ptr(partials), partials.shape[0], C, float(count), L.ptr(gamma), L.ptr(beta), float(eps), mom,

@@ -201,16 +201,18 @@ def decoder_tiles(ep: "EncoderPlan", sources, H: int, W: int) -> DecoderTiles:
     assert all(sp.Y * u == H and sp.X * u == W for sp, u in zip(st, ups))
     r = _decoder_tiles_launch([sp.map for sp in st], ups, B, H, W, st[0].map.device)
     n = int(r["n_act"].item())
-    ep.dec_tiles = DecoderTiles(sources, B, H, W, n, r["tile_slot"], r["tile_list"][:n], _site_rulebooks(st, ups, r["tile_slot"], H, W))
+    ep.dec_tiles = DecoderTiles(sources, B, H, W, n, r["tile_slot"], r["tile_list"][:n])
+    ep.dec_tiles.nbr = _site_rulebooks(ep.dec_tiles, st, ups)
     return ep.dec_tiles
 
 
-def decoder_site_rulebooks(dt: "DecoderTiles", sites, ups):
-    """Rulebooks of the conv_out backward for a tile set that came without them (inline plans): ``sites[g]`` = full-resolution
-    cells of source stage g's active sites, ``ups[g]`` its upsampling stride."""
+def decoder_site_rulebooks(dt: "DecoderTiles", sites, ups, n_tok=None):
+    """Per source stage the (n_sites, 9) rulebook of the conv_out backward (gdmae_decoder_site_rulebook): ``sites[g]`` = full-resolution
+    cells of source stage g's active sites, ``ups[g]`` its upsampling stride, ``n_tok[g]`` its token count (default: all the sites'
+    tokens).  Also called for a tile set that came without rulebooks (inline plans)."""
     out = []
-    for st, u in zip(sites, ups):
-        n_dev = torch.tensor([st.numel() // (u * u)], dtype=I32, device=st.device)
+    for g, (st, u) in enumerate(zip(sites, ups)):
+        n_dev = torch.tensor([st.numel() // (u * u) if n_tok is None else n_tok[g]], dtype=I32, device=st.device)
         nbr = _empty(st.numel() * 9, I32, st.device)
         L.call("gdmae_decoder_site_rulebook", L.ptr(st.contiguous()), L.ptr(n_dev), u * u, st.numel(), L.ptr(dt.tile_slot), dt.H, dt.W,
                L.ptr(nbr), L.stream())
@@ -218,18 +220,13 @@ def decoder_site_rulebooks(dt: "DecoderTiles", sites, ups):
     return out
 
 
-def _site_rulebooks(stages, ups, tile_slot, H, W):
-    """Per source stage the (n_sites, 9) rulebook of the conv_out backward (gdmae_decoder_site_rulebook)."""
-    out = []
-    for sp, u in zip(stages, ups):
-        sites = sp.tok_cell if u == 1 else (sp._up_sites[1] if getattr(sp, "_up_sites", None) is not None and sp._up_sites[0] == u
-                                            else upsample_cells(sp.tok_cell, sp.Y, sp.X, u).reshape(-1).contiguous())
-        n_dev = torch.tensor([sp.n_tok], dtype=I32, device=tile_slot.device)
-        nbr = _empty(sites.numel() * 9, I32, tile_slot.device)
-        L.call("gdmae_decoder_site_rulebook", L.ptr(sites.contiguous()), L.ptr(n_dev), u * u, sites.numel(), L.ptr(tile_slot), H, W, L.ptr(nbr),
-               L.stream())
-        out.append(nbr.view(-1, 9))
-    return out
+def _site_rulebooks(dt: "DecoderTiles", stages, ups):
+    """The rulebooks of a freshly built tile set, from the stage plans (their prepared upsampled sites where the stride matches; a
+    generator, so that a stage whose sites have to be computed does so right before its own rulebook launch)."""
+    sites = (sp.tok_cell if u == 1 else (sp._up_sites[1] if getattr(sp, "_up_sites", None) is not None and sp._up_sites[0] == u
+                                         else upsample_cells(sp.tok_cell, sp.Y, sp.X, u).reshape(-1).contiguous())
+             for sp, u in zip(stages, ups))
+    return decoder_site_rulebooks(dt, sites, ups, [sp.n_tok for sp in stages])
 
 
 def _encoder_launch(vox, m_cap: int, strides, window_shapes, drop_infos, keep_frac, noise, dec_sources=None) -> dict:

@@ -135,13 +135,29 @@ def test_no_rows_is_no_launch():
         assert L.load().gdmae_decoder_block_dw(None, None, None, None, None, 0, u, None, None, 24, 24, None, C, 0, None, None) == 0
 
 
-def _decoder_head_grads(mode, geo):
-    """one DecoderHead forward + backward on crafted stages (u = 1, 2, 4) with gdmae_hip.decoder.BLOCK_BWD = mode"""
+def _head_geometry():
+    """B = 2, 24 x 24, three source stages u = 1 / 2 / 4 with 150 / 37 / 13 tokens; pillars = the tokens of the first stage"""
+    d = torch.device("cuda:0")
+    B, H, W = 2, 24, 24
+    gen = torch.Generator().manual_seed(5)
+    stages = []
+    for u, ntok in ((1, 150), (2, 37), (4, 13)):
+        Ys, Xs = H // u, W // u
+        tok = torch.randperm(B * Ys * Xs, generator=gen)[:ntok].sort().values.int()
+        cmap = torch.full((B * Ys * Xs,), -1, dtype=torch.int32)
+        cmap[tok.long()] = torch.arange(ntok, dtype=torch.int32)
+        stages.append(types.SimpleNamespace(map=cmap.to(d), B=B, Y=Ys, X=Xs, tok_cell=tok.to(d), n_tok=ntok, _up_sites=None))
+    return (B, H, W, stages, stages[0].tok_cell, stages[0].map)
+
+
+def _decoder_head(geo, seed=11):
+    """one DecoderHead forward on the crafted stages: -> (outputs, leaves [conv_w, g2, b2, (P, g, b) per stage], tile set, an upstream
+    gradient for outputs[0])"""
     from gdmae_hip import decoder as gdec
     from gdmae_hip import plan as gplan
     d = torch.device("cuda:0")
     B, H, W, stages, pillar_cell, cell2pillar = geo
-    gen = torch.Generator().manual_seed(11)
+    gen = torch.Generator().manual_seed(seed)
     ep = types.SimpleNamespace(dec_tiles=None, stages=stages)
     dt = gplan.decoder_tiles(ep, (0, 1, 2), H, W)
     ups = [H // sp.Y for sp in stages]
@@ -155,11 +171,21 @@ def _decoder_head_grads(mode, geo):
         args += [sites, P, g, b]
         leaves += [P, g, b]
     up = torch.randn(pillar_cell.numel(), C, generator=gen).to(d)
+    geom = gdec.DecoderGeom(B, H, W, 1e-3, 1e-3, torch.bfloat16, gdec.TileConv(dt, [sp.map for sp in stages], ups))
+    outs = gdec.DecoderHead.apply(geom, None, conv_w, g2, b2, pillar_cell, cell2pillar, None, *args)
+    return outs, leaves, dt, up
+
+
+def _decoder_head_grads(mode, geo, mode_after_forward=None):
+    """one DecoderHead forward + backward on crafted stages (u = 1, 2, 4) with gdmae_hip.decoder.BLOCK_BWD = mode (and, if given,
+    = mode_after_forward between the forward and the backward)"""
+    from gdmae_hip import decoder as gdec
     old = gdec.BLOCK_BWD
     gdec.BLOCK_BWD = mode
     try:
-        outs = gdec.DecoderHead.apply((B, H, W, 1e-3, 1e-3, torch.bfloat16, (dt, [sp.map for sp in stages], ups), None), conv_w, g2, b2,
-                                      pillar_cell, cell2pillar, None, *args)
+        outs, leaves, _, up = _decoder_head(geo)
+        if mode_after_forward is not None:
+            gdec.BLOCK_BWD = mode_after_forward
         (outs[0] * up).sum().backward()
     finally:
         gdec.BLOCK_BWD = old
@@ -171,19 +197,7 @@ def test_decoder_head_backward_same_gradients_on_both_paths():
     """DecoderHead.backward with the block kernels (default) and with the rulebook path for every stage (GDMAE_DEC_BLOCK=0): dP, dgamma,
     dbeta of every stage and of the output BatchNorm bit-equal; the conv weight gradient bit-equal in the u = 1 stage's columns and
     within the bound of the C-ABI test per tap in the others."""
-    d = torch.device("cuda:0")
-    B, H, W = 2, 24, 24
-    gen = torch.Generator().manual_seed(5)
-    stages = []
-    for u, ntok in ((1, 150), (2, 37), (4, 13)):
-        Ys, Xs = H // u, W // u
-        tok = torch.randperm(B * Ys * Xs, generator=gen)[:ntok].sort().values.int()
-        cmap = torch.full((B * Ys * Xs,), -1, dtype=torch.int32)
-        cmap[tok.long()] = torch.arange(ntok, dtype=torch.int32)
-        stages.append(types.SimpleNamespace(map=cmap.to(d), B=B, Y=Ys, X=Xs, tok_cell=tok.to(d), n_tok=ntok, _up_sites=None))
-    pillar_cell = stages[0].tok_cell
-    cell2pillar = stages[0].map
-    geo = (B, H, W, stages, pillar_cell, cell2pillar)
+    geo = _head_geometry()
     new, ref = _decoder_head_grads("1", geo), _decoder_head_grads("0", geo)
     assert torch.equal(new[1], ref[1]) and torch.equal(new[2], ref[2]), "dgamma2 / dbeta2"
     for i in range(3):
@@ -199,3 +213,30 @@ def test_decoder_head_backward_same_gradients_on_both_paths():
     print("[decoder head backward] conv weight gradient, block vs rulebook path, worst tap: %.3e" % worst)
     assert worst <= 2 * PARENT_WORST, worst
     assert torch.equal(dw_new, dw_ref), "conv weight gradient: the two paths add the same products in the same order"
+
+
+def test_backward_schedule_is_the_one_the_forward_chose():
+    """gdmae_hip.decoder.BLOCK_BWD set to "0" after the forward and before backward(): the gradients are those of a run that never
+    touched it (bit for bit) - the forward decided the schedule and the backward consults no switch."""
+    geo = _head_geometry()
+    ref, got = _decoder_head_grads("1", geo), _decoder_head_grads("1", geo, mode_after_forward="0")
+    for i, (a, b) in enumerate(zip(got, ref)):
+        assert torch.equal(a, b), i
+
+
+def test_border_constants_belong_to_their_call():
+    """The dense expansion of head A's outputs is the same (bit for bit) before and after another head B, with another conv weight and
+    other BatchNorm parameters, has run: ybg travels with the call's outputs, not with the process."""
+    from gdmae_hip import decoder as gdec
+    geo = _head_geometry()
+    B, H, W = geo[:3]
+    a2 = (torch.rand(C, generator=torch.Generator().manual_seed(3)) + 0.5).cuda()
+    b2 = torch.randn(C, generator=torch.Generator().manual_seed(4)).cuda()
+    with torch.no_grad():
+        outs_a, _, dt, _ = _decoder_head(geo, seed=11)
+        first = gdec.expand_dense(outs_a[1], outs_a[-1], dt, a2, b2, B, H, W).clone()
+        outs_b = _decoder_head(geo, seed=23)[0]
+        assert not torch.equal(outs_b[-1], outs_a[-1]), "head B must have other border constants for this test to mean anything"
+        again = gdec.expand_dense(outs_a[1], outs_a[-1], dt, a2, b2, B, H, W)
+    torch.cuda.synchronize()
+    assert first.shape == (B, C, H, W) and torch.equal(first, again)
