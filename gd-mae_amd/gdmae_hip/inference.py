@@ -14,6 +14,7 @@ runs the whole head behind the pooling - graph network, shared layer, heads, box
 The trunk (everything up to the channels-last bf16 BEV map) is shared; the head is a variant.  The anchor variant never writes the
 dense per-anchor arrays: ``gdmae_anchor_head_infer`` goes from the BEV map to the anchors at or above SCORE_THRESH (score, label,
 decoded box, in anchor order) in two launches, and the top-k / NMS tail of ``post_processing`` runs on those survivors only.
+``engine.detect(batch_dict)`` (all three engines) runs that tail for the whole batch on the device and returns padded tensors.
 
 In evaluation mode every BatchNorm is a constant per-channel affine: a = gamma / sqrt(running_var + eps), b = beta - a running_mean.
 ``compile_detector`` folds it into the weights of the product in front of it (W' = a W per output channel, computed in fp64 and
@@ -728,6 +729,18 @@ class AnchorEngine(DetectorEngine):
                 pred, recall_dict = m.finish_sample(box[b, :n], score[b, :n], label[b, :n].long(), recall_dict, b, bd)
                 pred_dicts.append(pred)
             return pred_dicts, recall_dict
+
+    @torch.no_grad()
+    def detect(self, batch_dict):
+        """The trunk, the two-launch head, then the batched tail (``Detector3DTemplate.finish_batch``: three launches for all samples):
+        pred_boxes (B, n, 7), pred_scores (B, n), pred_labels (B, n) int64, num (B) int32 on the device, rows at or beyond num[b] zero;
+        n depends on the config only.  Nothing is read on the host after the trunk and no recall record is computed;
+        ``Detector3DTemplate.padded_to_pred_dicts`` gives the per-sample list of ``engine(batch_dict)``."""
+        self._check_fresh()
+        with torch.autocast("cuda", enabled=False):
+            _, x2, _, _, _ = self._trunk(batch_dict)
+            count, score, label, box, _ = self._head(x2, False)
+            return self.model.finish_batch(count, score, label, box)
 
 
 def compile_detector(model) -> DetectorEngine:

@@ -199,6 +199,8 @@ SIGNATURES = {
     "gdmae_anchor_head_infer_pack": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P]),
     "gdmae_anchor_head_infer_workspace_bytes": (_Z, [_I, _I, _I, _I]),
     "gdmae_anchor_head_infer": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _F, _F, _F, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "gdmae_anchor_detect_workspace_bytes": (_Z, [_I, _I]),
+    "gdmae_anchor_detect": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _F, _I, _P, _P, _P, _P, _P, _P]),
     "gdmae_boxes_bev_pairs": (_I, [_P, _I, _P, _I, _I, _P, _P]),
     "gdmae_nms_workspace_bytes": (_Z, [_I]),
     "gdmae_nms_bev": (_I, [_P, _I, _F, _I, _P, _P, _P, _P]),

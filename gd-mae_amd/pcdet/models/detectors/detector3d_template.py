@@ -235,6 +235,64 @@ class Detector3DTemplate(nn.Module):
                                                       thresh_list=cfg.RECALL_THRESH_LIST)
         return {'pred_boxes': final_boxes, 'pred_scores': final_scores, 'pred_labels': final_labels}, recall_dict
 
+    # ---- the same tail for the whole batch on the device (csrc/anchor_detect.hip)
+    def _batched_plan(self):
+        """(NMS_PRE_MAXSIZE, NMS_POST_MAXSIZE, NMS_THRESH) of ``finish_batch``; everything the batched tail does not build is refused
+        here by name."""
+        cfg = self.model_cfg.POST_PROCESSING
+        nms = cfg.NMS_CONFIG
+        if nms.MULTI_CLASSES_NMS:
+            raise NotImplementedError("finish_batch: MULTI_CLASSES_NMS: True (per-class NMS) is not built")
+        if not nms.get('NMS', True):
+            raise NotImplementedError("finish_batch: NMS: False (the batched tail is the NMS branch of post_processing)")
+        if cfg.get('OUTPUT_RAW_SCORE', False):
+            raise NotImplementedError("finish_batch: OUTPUT_RAW_SCORE True is not built")
+        if nms.NMS_TYPE != 'nms_gpu':
+            raise NotImplementedError(f"finish_batch: NMS_TYPE {nms.NMS_TYPE} (built: nms_gpu)")
+        pre, post = int(nms.NMS_PRE_MAXSIZE), int(nms.NMS_POST_MAXSIZE)
+        if pre > 4096:
+            raise NotImplementedError(f"finish_batch: NMS_PRE_MAXSIZE {pre} > 4096 (the candidates of a sample are sorted in LDS)")
+        if pre < 1 or post < 1:
+            raise NotImplementedError(f"finish_batch: NMS_PRE_MAXSIZE {pre} / NMS_POST_MAXSIZE {post} below 1")
+        return pre, post, float(nms.NMS_THRESH)
+
+    def batched_rows(self):
+        """Rows per sample of the padded output of ``finish_batch``: min(NMS_PRE_MAXSIZE, NMS_POST_MAXSIZE)."""
+        pre, post, _ = self._batched_plan()
+        return min(pre, post)
+
+    def finish_batch(self, count, scores, labels, boxes):
+        """``finish_sample`` for all samples in ``gdmae_anchor_detect`` (three launches, no host read), on the anchors at or above
+        SCORE_THRESH as ``gdmae_anchor_head_infer`` leaves them: ``count`` (B) int32, ``scores`` (B, A) fp32, ``labels`` (B, A) int32
+        1-based, ``boxes`` (B, A, 7) fp32; the first count[b] rows of a sample are read.  Ties in the score go to the earlier row, which
+        ``finish_sample`` leaves unspecified.  -> {'pred_boxes' (B, n, 7), 'pred_scores' (B, n), 'pred_labels' (B, n) int64, 'num' (B)
+        int32} on the device, n = ``batched_rows()``; rows at or beyond num[b] are zero (label 0).  No recall record."""
+        from gdmae_hip import lib as L
+        pre, post, thresh = self._batched_plan()
+        if not all(t.is_cuda for t in (count, scores, labels, boxes)):
+            raise NotImplementedError("finish_batch: CPU tensors (the tail runs in libgdmae_hip.so, no CPU fallback)")
+        B, A = scores.shape
+        if (count.dtype, scores.dtype, labels.dtype, boxes.dtype) != (torch.int32, torch.float32, torch.int32, torch.float32) or \
+                tuple(count.shape) != (B,) or tuple(labels.shape) != (B, A) or tuple(boxes.shape) != (B, A, 7):
+            raise NotImplementedError("finish_batch: count (B) int32, scores (B, A) fp32, labels (B, A) int32, boxes (B, A, 7) fp32")
+        dev = scores.device
+        n_out = min(pre, post)
+        out = {'pred_boxes': torch.empty(B, n_out, 7, dtype=torch.float32, device=dev),
+               'pred_scores': torch.empty(B, n_out, dtype=torch.float32, device=dev),
+               'pred_labels': torch.empty(B, n_out, dtype=torch.int64, device=dev),
+               'num': torch.empty(B, dtype=torch.int32, device=dev)}
+        ws = torch.empty(L.load().gdmae_anchor_detect_workspace_bytes(B, pre), dtype=torch.uint8, device=dev)
+        L.call("gdmae_anchor_detect", L.ptr(count), L.ptr(scores), L.ptr(labels), L.ptr(boxes), B, A, pre, post, thresh, n_out,
+               L.ptr(out['pred_boxes']), L.ptr(out['pred_scores']), L.ptr(out['pred_labels']), L.ptr(out['num']), L.ptr(ws), L.stream())
+        return out
+
+    @staticmethod
+    def padded_to_pred_dicts(out):
+        """The padded tensors of ``finish_batch`` -> the per-sample list ``post_processing`` returns.  ONE host read (``num``)."""
+        num = out['num'].tolist()
+        return [{'pred_boxes': out['pred_boxes'][b, :n], 'pred_scores': out['pred_scores'][b, :n], 'pred_labels': out['pred_labels'][b, :n]}
+                for b, n in enumerate(num)]
+
     def forward(self, **kwargs):
         raise NotImplementedError
 

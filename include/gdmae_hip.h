@@ -963,6 +963,19 @@ int gdmae_anchor_head_infer(const void* X, int B, int H, int W, int cin, int K, 
                             const float* yc, const float* slot, float dir_offset, float dir_limit_offset, float thresh,
                             float* rows_out, int* count, int* idx, float* score, int* label, float* box, void* workspace,
                             void* stream);
+/* The tail behind gdmae_anchor_head_infer for all samples in three launches, nothing read on the host (csrc/anchor_detect.hip, DESIGN
+ * 7m; Detector3DTemplate.finish_sample made deterministic).  count (B), score (B, A) >= 0, label (B, A) int32 1-based, box (B, A, 7)
+ * as gdmae_anchor_head_infer leaves them: the first count[b] rows of a sample are read, nothing behind them.  Per sample: the rows in
+ * (score descending, row position ascending) order, the first min(count[b], pre_max) enter the rotated NMS (a box is suppressed by a
+ * kept earlier box with bev_iou > nms_thresh, the bev_iou of gdmae_nms_bev), the first post_max kept boxes are emitted in that order
+ * with their input bits; a kept row with label 0 is dropped behind that cut.  n_out = min(pre_max, post_max).  Outputs fully written:
+ * boxes (B, n_out, 7), scores (B, n_out), labels (B, n_out) int64, num (B) int32; rows at or beyond num[b] are zero (label 0).  A
+ * sample's rows depend on that sample only; two calls agree bit for bit.  Errors: B < 1, A < 1, pre_max outside 1 .. 4096,
+ * post_max < 1, a negative or NaN threshold, a wrong n_out, a null pointer.  workspace_bytes: 0 for what the entry refuses. */
+size_t gdmae_anchor_detect_workspace_bytes(int B, int pre_max);
+int gdmae_anchor_detect(const int* count, const float* score, const int* label, const float* box, int B, int A, int pre_max,
+                        int post_max, float nms_thresh, int n_out, float* boxes, float* scores, long long* labels, int* num,
+                        void* workspace, void* stream);
 
 /* ---- a21: fused optimizer step over one flat buffer ------------------------------------------- *
  * Replaces clip_grad_norm_ (tools/train_utils/train_utils.py:52) and OptimWrapper.step

@@ -12,8 +12,9 @@ row product on the library GEMM + gdmae_anchor_decode + gdmae_anchor_select.
 
 --config ts: the two-stage GraphRCNN detector of configs.waymo_two_stage_cfg() (Waymo-shape grid and cloud, CenterHead with
 multi_class_nms over three classes, then the RoI head); it has engine paths only.  --path detect: ``engine.detect`` (the batched
-CenterHead tail) against ``engine(batch_dict)`` (the op-by-op tail: what the engine call has been since the engines were
-added), alternating; then the two tails alone on the same head maps, with their launch counts.
+CenterHead tail; with --config kitti the batched anchor-head tail) against ``engine(batch_dict)`` (the
+op-by-op tail: what the engine call has been since the engines were added), alternating; then the two tails alone on the same head
+maps (--config kitti: on the same survivors of the head), with their launch counts.
 
 Prints every run pair, the medians, frames/s, the kernel-launch count of one engine call and of one parent call (torch profiler,
 device activity), and the bytes of the encoder's backward-only side outputs one engine call writes.  --path engine | parent runs one
@@ -122,6 +123,42 @@ def tails_alone(eng, net, pts, B, args):
           f"batched / op-by-op = {a / b:.3f}", flush=True)
 
 
+def anchor_tails_alone(eng, net, pts, B, args):
+    """The anchor-head tail alone on the same ``_head`` output: the host read of the counts + the ``finish_sample`` loop (per sample a
+    top-k, three gathers, a sort, a two-launch NMS and a host read) against ``finish_batch`` (three launches)."""
+    with torch.no_grad(), torch.autocast("cuda", enabled=False):
+        x2 = eng._trunk({"points": pts, "batch_size": B})[1]
+        count, score, label, box, _ = eng._head(x2, False)
+
+    def old():
+        with torch.no_grad(), torch.autocast("cuda", enabled=False):
+            counts = count.tolist()
+            recall, preds = {}, []
+            for b in range(B):
+                n = counts[b]
+                pred, recall = net.finish_sample(box[b, :n], score[b, :n], label[b, :n].long(), recall, b, {"batch_size": B})
+                preds.append(pred)
+            return preds
+
+    def new():
+        with torch.no_grad(), torch.autocast("cuda", enabled=False):
+            return net.finish_batch(count, score, label, box)
+    for fn in (new, old):
+        for _ in range(args.warmup):
+            fn()
+    torch.cuda.synchronize()
+    print(f"batch {B} tail alone: survivors per sample {count.tolist()}; boxes per sample, batched {new()['num'].tolist()}  "
+          f"op-by-op {[int(d['pred_boxes'].shape[0]) for d in old()]}", flush=True)
+    res = {"new": [], "old": []}
+    for r in range(args.runs):
+        res["new"].append(timed(new, args.calls))
+        res["old"].append(timed(old, args.calls))
+        print(f"batch {B} tail run {r}: batched {res['new'][-1]:.3f} ms  op-by-op {res['old'][-1]:.3f} ms", flush=True)
+    a, b = statistics.median(res["new"]), statistics.median(res["old"])
+    print(f"batch {B} tail alone: batched {a:.3f} ms ({launches(new)} launches), op-by-op {b:.3f} ms ({launches(old)} launches), "
+          f"batched / op-by-op = {a / b:.3f}", flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default="D", choices=["D", "kitti", "ts"])
@@ -144,8 +181,6 @@ def main():
             ap.error("--config ts has engine paths only: use --path detect")
     else:
         cfg, ds, skw = configs.named_config("D")
-    if args.path == "detect" and args.config == "kitti":
-        ap.error("--path detect: the anchor-head engine has its own fused tail")
     torch.manual_seed(3)
     net = build_network(cfg, len(ds.class_names), ds, logging.getLogger("bench")).to(dev).eval()
     g = torch.Generator().manual_seed(5)
@@ -198,7 +233,7 @@ def main():
             head_alone(eng, net, pts, B, args)
         if args.path == "detect":
             print(f"batch {B}: detect / engine median = {statistics.median(res['detect']) / statistics.median(res['engine']):.3f}", flush=True)
-            tails_alone(eng, net, pts, B, args)
+            (anchor_tails_alone if args.config == "kitti" else tails_alone)(eng, net, pts, B, args)
             continue
         if args.path != "parent" and not args.no_launch_count:
             maps = eng.head_maps({"points": pts, "batch_size": B})
