@@ -1,7 +1,8 @@
 """``GraphRCNN``: the two-stage detector of tools/cfgs/waymo_models/gd_mae_ts.yaml in eval mode (reference
 pcdet/models/detectors/graph_rcnn.py:4-25): module loop, then ``post_processing`` (its ``NMS: False`` branch for the shipped
 config).  ``FREEZE_LAYERS`` is accepted: freezing the first stage is a training concern and has no effect in eval.
-Second-stage training is not built: the RoI head raises in training mode."""
+Training mode of this module keeps raising; the second stage trains through ``gdmae_hip.two_stage.SecondStageTrainer``,
+which reads ``FREEZE_LAYERS``."""
 from .detector3d_template import Detector3DTemplate
 
 

@@ -5,8 +5,11 @@ RoI point pooling runs through ``pcdet.ops.patch_ops`` (device tensors: the HIP 
 the whole batch; CPU tensors: the numpy statement of the same contract).  The graph network, the shared layer and the two
 heads are plain torch modules in fp32 - the exact mode, as for the other detectors.
 
-Not built, raised by name: training mode (proposal target layer, rcnn losses), ``IMG_CONFIG`` (the image branch),
-``USE_FEATS_DIS: True`` and a non-None ``NMS_CONFIG.TEST`` (RoI selection inside the head)."""
+Training runs through ``forward_train`` (proposal targets from ``gdmae_roi_targets``, then the same pooling, graph network and
+heads with autograd), driven by ``gdmae_hip.two_stage.SecondStageTrainer``; ``forward`` in training mode keeps raising.
+
+Not built, raised by name: ``IMG_CONFIG`` (the image branch), ``USE_FEATS_DIS: True`` and a non-None ``NMS_CONFIG.TEST`` /
+``NMS_CONFIG.TRAIN`` (RoI selection inside the head)."""
 import numpy as np
 import torch
 import torch.nn as nn
@@ -161,6 +164,29 @@ class GraphRCNNHead(RoIHeadTemplate):
         batch_dict['batch_cls_preds'] = torch.pow(torch.sigmoid(batch_cls_preds), 0.5) * torch.pow(roi_scores.unsqueeze(-1), 0.5)
         batch_dict['batch_box_preds'] = batch_box_preds
         batch_dict['cls_preds_normalized'] = True
+        return batch_dict
+
+    def forward_train(self, batch_dict, u_fg, u_bg):
+        """One training forward (graphrcnn_head.py:254-301 with ``self.training``): proposal targets for the first stage's RoIs
+        (``u_fg (B, M)``, ``u_bg (B, ROI_PER_IMAGE)`` decide the sampling), ``rois`` / ``roi_labels`` replaced by the sampled ones,
+        pooling, graph network, heads; the result is left in ``forward_ret_dict`` for ``rcnn_losses`` (the reference's keys, and
+        ``pooled_feats_local``: what the graph network was fed)."""
+        if not _is_none(self.model_cfg.NMS_CONFIG.get('TRAIN', None)):
+            raise NotImplementedError("ROI_HEAD.NMS_CONFIG.TRAIN (RoI selection by NMS inside the head) is not built")
+        self.proposal_layer(batch_dict, nms_config=None)
+        targets_dict = self.proposal_targets(batch_dict, u_fg, u_bg)
+        batch_dict['rois'] = targets_dict['rois']
+        batch_dict['roi_labels'] = targets_dict['roi_labels']
+        B, M, _ = batch_dict['rois'].shape
+        with torch.no_grad():
+            roi_feats_local, _, roi_points_num = self.roipool3d_gpu(batch_dict)
+            roi_feats_local = roi_feats_local * (roi_points_num > 0).unsqueeze(-1).unsqueeze(-1)
+        rcnn_cls, rcnn_reg = self.heads(self.pooled_to_features(roi_feats_local, B, M), B, M)
+        targets_dict['rcnn_cls'] = rcnn_cls
+        targets_dict['rcnn_reg'] = rcnn_reg
+        targets_dict['batch_size'] = batch_dict['batch_size']
+        targets_dict['pooled_feats_local'] = roi_feats_local
+        self.forward_ret_dict = targets_dict
         return batch_dict
 
     def pooled_to_features(self, roi_feats_local, B, M):

@@ -1043,6 +1043,31 @@ int gdmae_roi_graph_forward(const float* feats_local, const int* pooled_num, con
                             float* rcnn_cls, float* rcnn_reg, float* batch_box_preds, float* batch_cls_preds, int* nbr_debug,
                             void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- proposal targets of the second stage (csrc/roi_targets.hip; ProposalTargetLayer, proposal_target_layer.py:13-230, and the
+ * canonical transformation of RoIHeadTemplate.assign_targets, roi_head_template.py:104-127) -------------------------- *
+ * rois (batch, n_rois, roi_cols = 7) fp32, roi_scores (batch, n_rois) fp32, roi_labels (batch, n_rois) int32 1-based (0: padded
+ * row), gt_boxes (batch, n_gt, 8) fp32 with the label in the last column, u_fg (batch, n_rois) and u_bg (batch, rois_per_image)
+ * fp32 uniform numbers in [0, 1), hard_quota (rois_per_image + 1) int32 = int(nb * HARD_BG_RATIO) per number of background slots;
+ * all device.  by_class: SAMPLE_ROI_BY_EACH_CLASS; cls_score_type: 0 = roi_iou, 1 = cls.
+ * Valid GT rows: 0 .. last row with a non-zero entry.  Overlap: bev_overlap x height overlap / max(vol_a + vol_b - overlap, 1e-6);
+ * the lowest GT row (of the RoI's label when by_class) with the largest overlap, row 0 with overlap 0 when there is none.
+ * fg: overlap >= min(reg_fg, cls_fg); easy bg: < cls_bg_lo; hard bg: the rest below reg_fg; each list in RoI order.
+ * f = min(fg_per_image, n_fg) fg RoIs with the smallest (u_fg, RoI index) fill slots 0 .. f - 1 in that order; of the remaining
+ * nb slots the first min(hard_quota[nb], n_hard) draw from the hard list and the rest from the easy list (all from the one list
+ * that is not empty), slot j taking element min(int(u_bg[j] n), n - 1); without any background every slot draws from the fg list.
+ * Outputs, rois_per_image rows per sample: out_rois (.., 7), out_roi_scores, out_roi_labels int32, out_roi_indices int32,
+ * out_gt_iou, out_gt_src (.., 8) the assigned GT row, out_gt_of_rois (.., 8) the same in the RoI's canonical frame,
+ * out_reg_valid int32 (overlap > reg_fg), out_cls_labels fp32 (roi_iou: 1 above cls_fg, 0 below cls_bg, linear between; cls: 1 / 0,
+ * -1 strictly between).  Refused (non-zero): roi_cols != 7, n_rois, n_gt or rois_per_image outside 1 .. 1024.
+ * workspace: gdmae_roi_targets_workspace_bytes(batch, n_rois) bytes.  Two launches, no atomics, no host synchronisation. */
+size_t gdmae_roi_targets_workspace_bytes(int batch, int n_rois);
+int gdmae_roi_targets(const float* rois, const float* roi_scores, const int* roi_labels, int batch, int n_rois, int roi_cols,
+                      const float* gt_boxes, int n_gt, const float* u_fg, const float* u_bg, const int* hard_quota,
+                      int rois_per_image, int fg_per_image, float reg_fg_thresh, float cls_fg_thresh, float cls_bg_thresh,
+                      float cls_bg_thresh_lo, int by_class, int cls_score_type, float* out_rois, float* out_roi_scores,
+                      int* out_roi_labels, int* out_roi_indices, float* out_gt_iou, float* out_gt_src, float* out_gt_of_rois,
+                      int* out_reg_valid, float* out_cls_labels, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
