@@ -9,7 +9,7 @@
 //                bitonic sort of (u_fg bits, RoI index) keys in LDS, then one thread per output slot draws its RoI and writes its row of
 //                every output (copied rows, labels, GT in the RoI's canonical frame).
 // Keys are unique (the RoI index is in them) and there are no atomics: the result does not depend on scheduling.
-#include "bev_iou.h"
+#include "iou3d_rows.h"
 
 namespace {
 constexpr int kRtMax = 1024;      // RoIs, GT rows and output slots per sample (LDS lists, 10-bit counters)
@@ -17,34 +17,6 @@ constexpr int kRtMax = 1024;      // RoIs, GT rows and output slots per sample (
 struct RtThresh {
   float reg_fg, cls_fg, cls_bg, cls_bg_lo;
 };
-
-// rows 0 .. k of a sample's GT table are valid, k = last row with a non-zero entry (0 when there is none): whole wavefront
-__device__ inline int rt_valid_rows(const float* __restrict__ gt, int G, int lane) {
-  int last = 0;
-  for (int g = lane; g < G; g += GD_WAVE) {
-    bool any = false;
-#pragma unroll
-    for (int c = 0; c < 8; ++c) any = any || gt[(size_t)g * 8 + c] != 0.f;
-    if (any) last = g;
-  }
-#pragma unroll
-  for (int d = GD_WAVE / 2; d > 0; d >>= 1) last = max(last, __shfl_xor(last, d, GD_WAVE));
-  return last + 1;
-}
-
-__device__ inline float rt_iou3d(const float* a, const float* b) {
-  const float a_max = a[2] + a[5] / 2, a_min = a[2] - a[5] / 2;
-  const float b_max = b[2] + b[5] / 2, b_min = b[2] - b[5] / 2;
-  const float oh = fmaxf(fminf(a_max, b_max) - fmaxf(a_min, b_min), 0.f);
-  // centres further apart than the half-diagonals (+ 0.1 m, far beyond the 1e-2 margin of the corner test): no crossing, no corner
-  // inside the other box, the polygon is empty and bev_overlap returns exactly 0
-  const float ra = 0.5f * sqrtf(a[3] * a[3] + a[4] * a[4]), rb = 0.5f * sqrtf(b[3] * b[3] + b[4] * b[4]);
-  const float dx = a[0] - b[0], dy = a[1] - b[1], reach = ra + rb + 0.1f;
-  const float ov = (dx * dx + dy * dy > reach * reach) ? 0.f : bev_overlap(a, b);
-  const float o3 = ov * oh;
-  const float va = a[3] * a[4] * a[5], vb = b[3] * b[4] * b[5];
-  return o3 / fmaxf(va + vb - o3, 1e-6f);
-}
 
 __global__ __launch_bounds__(256) void k_rt_match(const float* __restrict__ rois, const int* __restrict__ labels, const float* __restrict__ gt, int M,
                                                   int G, int by_class, float* __restrict__ iou_out, int* __restrict__ row_out) {

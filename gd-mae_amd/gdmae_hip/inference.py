@@ -14,7 +14,8 @@ runs the whole head behind the pooling - graph network, shared layer, heads, box
 The trunk (everything up to the channels-last bf16 BEV map) is shared; the head is a variant.  The anchor variant never writes the
 dense per-anchor arrays: ``gdmae_anchor_head_infer`` goes from the BEV map to the anchors at or above SCORE_THRESH (score, label,
 decoded box, in anchor order) in two launches, and the top-k / NMS tail of ``post_processing`` runs on those survivors only.
-``engine.detect(batch_dict)`` (all three engines) runs that tail for the whole batch on the device and returns padded tensors.
+``engine.detect(batch_dict)`` (all three engines) runs that tail for the whole batch on the device and returns padded tensors;
+``engine.detect(batch_dict, recall=record)`` also adds the batch's recall figures to a ``gdmae_hip.evaluation.RecallRecord``.
 
 In evaluation mode every BatchNorm is a constant per-channel affine: a = gamma / sqrt(running_var + eps), b = beta - a running_mean.
 ``compile_detector`` folds it into the weights of the product in front of it (W' = a W per output channel, computed in fp64 and
@@ -75,6 +76,14 @@ def _block(seq, kind):
     if len(mods) != 3 or not isinstance(mods[0], kind) or not isinstance(mods[2], nn.ReLU):
         _no(f"expected Sequential({kind.__name__}, BatchNorm, ReLU), got {[type(m).__name__ for m in mods]}")
     return mods[0], mods[1]
+
+
+def _record(model, recall, batch_dict):
+    """The ``RecallRecord`` a ``detect`` call updates, or None (``evaluation.post_cfg_record``: thresholds checked before anything runs)."""
+    if recall is None:
+        return None
+    from . import evaluation
+    return evaluation.post_cfg_record(model.model_cfg.POST_PROCESSING, recall, batch_dict)
 
 
 class _Dense:
@@ -461,14 +470,20 @@ class CenterPointEngine(DetectorEngine):
             return m.post_processing(bd)
 
     @torch.no_grad()
-    def detect(self, batch_dict):
+    def detect(self, batch_dict, recall=None):
         """``head_maps``, then the batched tail (``CenterHead.generate_predicted_boxes_batched``: three launches for all samples and
         classes): pred_boxes (B, n, 7 | 9), pred_scores (B, n), pred_labels (B, n) int64, num (B) int32 on the device, rows at or beyond
-        num[b] zero; n depends on the config only.  Nothing is read on the host after the trunk and no recall record is computed;
-        ``CenterHead.padded_to_pred_dicts`` gives the per-sample list of ``engine(batch_dict)``."""
+        num[b] zero; n depends on the config only.  Nothing is read on the host after the trunk;
+        ``CenterHead.padded_to_pred_dicts`` gives the per-sample list of ``engine(batch_dict)``.  ``recall``: a
+        ``gdmae_hip.evaluation.RecallRecord`` that receives the batch's recall figures (two more launches, still no host read) when
+        ``batch_dict`` has ``gt_boxes``; without either, no recall record is computed."""
+        rec = _record(self.model, recall, batch_dict)
         maps = self.head_maps(batch_dict)
         with torch.autocast("cuda", enabled=False):
-            return self.model.dense_head.generate_predicted_boxes_batched(int(batch_dict['batch_size']), maps)
+            out = self.model.dense_head.generate_predicted_boxes_batched(int(batch_dict['batch_size']), maps)
+            if rec is not None:
+                rec.update(out['pred_boxes'], out['num'], batch_dict['gt_boxes'])
+            return out
 
 
 ROI_GRAPH_CONFIG = {'IN_DIM': 11, 'MLPS': [32, 32, 64], 'CALIB_DIM': 64, 'EXP_MLPS': [512], 'OUT_DIM': 256, 'K': 8, 'USE_FEATS_DIS': False,
@@ -614,13 +629,15 @@ class GraphRCNNEngine(CenterPointEngine):
             return self.model.post_processing(bd)
 
     @torch.no_grad()
-    def detect(self, batch_dict):
+    def detect(self, batch_dict, recall=None):
         """Both stages on padded device tensors: the first stage through the batched tail, its padded output as the RoIs, then the
         second stage.  ONE host read in between, ``num.max()``: the RoI rows are trimmed to M = max(1, largest count of the batch), the M
         of ``proposals()``, so the second stage runs as many rows as ``engine(batch_dict)`` does and no more.  -> pred_boxes (B, M, 7),
         pred_scores (B, M), pred_labels (B, M) int64 (the RoI labels; 0 in padded rows, whose boxes and scores are zero), num (B).
-        No recall record."""
+        ``recall``: as in ``CenterPointEngine.detect``, with the refined boxes as the rcnn side and the RoIs as the roi side (what
+        ``post_processing_without_nms`` hands ``generate_recall_record``)."""
         B = int(batch_dict['batch_size'])
+        rec = _record(self.model, recall, batch_dict)
         first = super().detect(batch_dict)
         M = max(1, int(first['num'].max()))                       # the host read
         with torch.autocast("cuda", enabled=False):
@@ -629,8 +646,11 @@ class GraphRCNNEngine(CenterPointEngine):
             out = self._second_stage(batch_dict['points'], B, rois, first['pred_scores'][:, :M].contiguous(), True)
             real = labels != 0
             boxes, scores = out['batch_box_preds'], out['batch_cls_preds'].max(dim=-1)[0]
-            return {'pred_boxes': torch.where(real.unsqueeze(-1), boxes, torch.zeros_like(boxes)),
-                    'pred_scores': torch.where(real, scores, torch.zeros_like(scores)), 'pred_labels': labels, 'num': first['num']}
+            res = {'pred_boxes': torch.where(real.unsqueeze(-1), boxes, torch.zeros_like(boxes)),
+                   'pred_scores': torch.where(real, scores, torch.zeros_like(scores)), 'pred_labels': labels, 'num': first['num']}
+            if rec is not None:
+                rec.update(res['pred_boxes'], res['num'], batch_dict['gt_boxes'], rois=rois, roi_num=first['num'])
+            return res
 
 
 class AnchorEngine(DetectorEngine):
@@ -731,16 +751,21 @@ class AnchorEngine(DetectorEngine):
             return pred_dicts, recall_dict
 
     @torch.no_grad()
-    def detect(self, batch_dict):
+    def detect(self, batch_dict, recall=None):
         """The trunk, the two-launch head, then the batched tail (``Detector3DTemplate.finish_batch``: three launches for all samples):
         pred_boxes (B, n, 7), pred_scores (B, n), pred_labels (B, n) int64, num (B) int32 on the device, rows at or beyond num[b] zero;
-        n depends on the config only.  Nothing is read on the host after the trunk and no recall record is computed;
-        ``Detector3DTemplate.padded_to_pred_dicts`` gives the per-sample list of ``engine(batch_dict)``."""
+        n depends on the config only.  Nothing is read on the host after the trunk;
+        ``Detector3DTemplate.padded_to_pred_dicts`` gives the per-sample list of ``engine(batch_dict)``.  ``recall``: as in
+        ``CenterPointEngine.detect``."""
         self._check_fresh()
+        rec = _record(self.model, recall, batch_dict)
         with torch.autocast("cuda", enabled=False):
             _, x2, _, _, _ = self._trunk(batch_dict)
             count, score, label, box, _ = self._head(x2, False)
-            return self.model.finish_batch(count, score, label, box)
+            out = self.model.finish_batch(count, score, label, box)
+            if rec is not None:
+                rec.update(out['pred_boxes'], out['num'], batch_dict['gt_boxes'])
+            return out
 
 
 def compile_detector(model) -> DetectorEngine:

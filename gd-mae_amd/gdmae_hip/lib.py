@@ -213,6 +213,7 @@ SIGNATURES = {
     "gdmae_roi_dfvs_pool": (_I, [_P, _L, _I, _P, _I, _I, _I, _P, _P, _I, _I, _P, _I, _I, _I, _F, _F, _I, _I, _P, _P, _P, _P, _P, _Z, _P]),
     "gdmae_roi_targets_workspace_bytes": (_Z, [_I, _I]),
     "gdmae_roi_targets": (_I, [_P, _P, _P, _I, _I, _I, _P, _I, _P, _P, _P, _I, _I, _F, _F, _F, _F, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
+    "gdmae_recall_record": (_I, [_P, _P, _I, _I, _I, _P, _P, _I, _I, _P, _I, _I, _P, _I, _P, _P, _P]),
     "gdmae_roi_graph_folded_floats": (_Z, []),
     "gdmae_roi_graph_packed_bytes": (_Z, []),
     "gdmae_roi_graph_workspace_bytes": (_Z, [_L]),

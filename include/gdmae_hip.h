@@ -1068,6 +1068,24 @@ int gdmae_roi_targets(const float* rois, const float* roi_scores, const int* roi
                       int* out_roi_labels, int* out_roi_indices, float* out_gt_iou, float* out_gt_src, float* out_gt_of_rois,
                       int* out_reg_valid, float* out_cls_labels, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- recall record of an evaluation step (csrc/recall_record.hip; Detector3DTemplate.generate_recall_record,
+ * detector3d_template.py:318-358, for the whole batch) --------------------------------------------------------------- *
+ * pred_boxes (batch, n_pred, pred_cols >= 7) fp32 and pred_num (batch) int32, or NULL for "all n_pred rows": rows at or beyond
+ * pred_num[b] are not read.  rois (batch, n_rois, roi_cols >= 7) fp32 with roi_num the same way, or rois NULL: no RoI side (n_rois
+ * and roi_cols are still checked; pass 0 and 7).  gt_boxes (batch, n_gt, gt_cols >= 7) fp32.  The first 7 columns of a row are read.
+ * All device; thresholds: n_thresh (1 .. 8) HOST floats.
+ * Valid GT rows of a sample: 0 .. last row with a non-zero entry, none without one (an all-zero row in between counts and is never
+ * recalled).  IoU: bev_overlap(pred, gt) x height overlap / max(vol_pred + vol_gt - overlap, 1e-6), the operations of
+ * boxes_iou3d_gpu.  best_iou (batch, n_gt, 2) fp32, written on every call: each GT row's largest IoU over the RoI rows [.., 0] and
+ * over the predicted rows [.., 1]; 0 where there are none and in GT rows at or beyond the valid count.
+ * counters (1 + 2 n_thresh) int64 = [gt_num, roi_t0 .. , rcnn_t0 ..]: the call ADDS the batch's valid GT rows and, per threshold,
+ * the valid rows whose largest IoU is > t (fp32); the roi counters move only when rois is given.  It is never read on the host.
+ * Refused (non-zero, nothing launched): n_thresh outside 1 .. 8, any *_cols < 7, a negative batch / n_pred / n_rois / n_gt.
+ * n_pred, n_rois, n_gt of 0 are legal.  Two launches, no atomics, no workspace, no host synchronisation. */
+int gdmae_recall_record(const float* pred_boxes, const int* pred_num, int batch, int n_pred, int pred_cols, const float* rois,
+                        const int* roi_num, int n_rois, int roi_cols, const float* gt_boxes, int n_gt, int gt_cols,
+                        const float* thresholds, int n_thresh, long long* counters, float* best_iou, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
