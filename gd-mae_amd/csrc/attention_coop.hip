@@ -196,8 +196,8 @@ __device__ __forceinline__ void coop_fwd(const CArgs& A, const unsigned blk, uns
 
 // ---------------------------------------------------------------------------------------------------------------------
 // backward.  The forward left lse[token][head] = log2 sum_k exp(logit) (coop_fwd), and D[query] = sum_k P dP = dO[query] . O[query] is a
-// row dot product of the saved attention output - so nothing about a query has to be reduced over the keys here: a probability is
-// p = exp2(logit log2(e) - lse) wherever it is needed.  Phase 1 (this wave's 32 queries, S^T layout) walks the key tiles one at a time
+// row dot product of the saved attention output - so nothing about a query has to be reduced over the keys before dS can be formed: a
+// probability is p = exp2(logit log2(e) - lse) wherever it is needed (dtau alone carries two row sums along, see phase 1).  Phase 1 (this wave's 32 queries, S^T layout) walks the key tiles one at a time
 // with 32 instead of 64 accumulator registers live; phase 2 (this wave's 32 keys, S layout) needs nothing from phase 1.  <= 128
 // registers: four wavefronts per SIMD (the two-pass form needed 197), and the sparse level can share the launch.
 // ---------------------------------------------------------------------------------------------------------------------
@@ -300,7 +300,7 @@ __device__ __forceinline__ void coop_bwd(const CBwdArgs& A, const unsigned blk, 
     const float qa = qin * inv_tau, qc = qa * kLog2e;
     const float lse = sLse[r], D = sD[r];
     f32x16 oq = splat(0.f);
-    float dt = 0.f;
+    float dt = 0.f, pt = 0.f, sds = 0.f;
 #pragma unroll
     for (int kj = 0; kj < NW; ++kj) {
       const Row<NPC> kk = lds_row<NPC>(tK, 32 * kj + rho, h), vv = lds_row<NPC>(tV, 32 * kj + rho, h);
@@ -314,12 +314,17 @@ __device__ __forceinline__ void coop_bwd(const CBwdArgs& A, const unsigned blk, 
         const float p = __builtin_amdgcn_exp2f(fmaf(t, qc, -lse));
         const float ds = p * aP[e];
         dt = fmaf(ds, t, dt);
+        pt = fmaf(p, t, pt);
+        sds += ds;
         aS[e] = ds * kr[e];                                                          // dS / |k|: the A operand is the raw K row
       }
       oq = mma_tokens(tK + 32 * kj * kPitch, aS, oq, lane);                          // dQ^^T[dh][query] (without 1 / tau)
       __builtin_amdgcn_sched_barrier(0);
     }
-    // sum_keys dS a = qa sum dS t over this lane's keys; d a / d tau = -a / tau
+    // sum_keys dS a = qa sum dS t over this lane's keys; d a / d tau = -a / tau.  A row of dS sums to zero only with the exact D; D
+    // here is dO . O with O rounded to bf16, and the row's residue sum dS = D_exact - D would enter multiplied by the row's mean t
+    // (logits of 1 / tau_min: orders of magnitude above dtau itself).  Taking t relative to that mean, sum dS (t - sum p t), removes it.
+    dt = fmaf(-half_sum(pt), sds, dt);
     dtau = -dt * (qa * inv_tau);
     float qh[NPC][4], pr = 0.f;
 #pragma unroll
