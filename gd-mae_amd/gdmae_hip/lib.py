@@ -214,6 +214,9 @@ SIGNATURES = {
     "gdmae_roi_targets_workspace_bytes": (_Z, [_I, _I]),
     "gdmae_roi_targets": (_I, [_P, _P, _P, _I, _I, _I, _P, _I, _P, _P, _P, _I, _I, _F, _F, _F, _F, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
     "gdmae_recall_record": (_I, [_P, _P, _I, _I, _I, _P, _P, _I, _I, _P, _I, _I, _P, _I, _P, _P, _P]),
+    "gdmae_kitti_eval_frames_per_chunk": (_I, []),
+    "gdmae_kitti_eval_workspace_bytes": (_Z, [_I, _I]),
+    "gdmae_kitti_eval": (_I, [_I, _I, _I] + [_P] * 21 + [_I] + [_P] * 9 + [_Z, _P]),
     "gdmae_roi_graph_folded_floats": (_Z, []),
     "gdmae_roi_graph_packed_bytes": (_Z, []),
     "gdmae_roi_graph_workspace_bytes": (_Z, [_L]),

@@ -1086,6 +1086,34 @@ int gdmae_recall_record(const float* pred_boxes, const int* pred_num, int batch,
                         const int* roi_num, int n_rois, int roi_cols, const float* gt_boxes, int n_gt, int gt_cols,
                         const float* thresholds, int n_thresh, long long* counters, float* best_iou, void* stream);
 
+/* ---- official KITTI AP statistics (csrc/kitti_eval.hip; kitti_object_eval_python/eval.py: calculate_iou_partly,
+ * compute_statistics_jit, get_thresholds, fused_compute_statistics) -------------------------------------------------- *
+ * Frames are concatenated: gt_off / dt_off / dc_off (n_frames + 1) int32 are the row offsets of the GT, detection and DontCare tables,
+ * given twice: host_* on the HOST (checked here) and on the device (read by the kernels); pair_off (n_frames + 1) int64 device: the
+ * running sum of G_f * D_f.  gt_box / dt_box / dc_box (rows, 4) image boxes, gt_geo / dt_geo (rows, 7) = location (3), dimensions (3),
+ * rotation_y in camera coordinates, *_alpha and dt_score (rows), all fp32 device.  ignored_gt (CL, NG) / ignored_dt (CL, ND) int8: the
+ * reference's clean_data flags (0, 1, -1) per (class, difficulty) row.  A combination c of n_combos uses flag row combo_cl[c], overlap
+ * combo_metric[c] (0 bbox, 1 bev, 2 3d), the fp64 combo_min_overlap[c] and the valid-GT count combo_num_gt[c] (device arrays).
+ * stages == 1: overlaps (3, NP) fp32 (per frame GT-major: [g * D_f + d]), dc_max (ND) fp32 (largest criterion-0 image overlap with a
+ *   DontCare box of the frame) and matched (n_combos, NG) fp32 (the score of the first pass's true positive of a GT row, -inf elsewhere)
+ *   are written.  Two launches.
+ * stages == 2: sorted_scores (n_combos, NG) = every row of `matched` in descending order; writes thresholds (n_combos, 41) fp32
+ *   (0 behind the count), n_thresholds (n_combos) int32, pr_counts (n_combos, 41, 3) int64 = tp, fp, fn and pr_sim (n_combos, 41) fp64
+ *   (the AOS similarity sum; 0 unless compute_aos and the combination's metric is 0).  Three launches; workspace: gdmae_kitti_eval_workspace_bytes bytes.
+ * Scores and overlaps are compared as fp32 values (an overlap widened to fp64 against min_overlap).  Sums over frames run in a fixed
+ * order (gdmae_kitti_eval_frames_per_chunk frames per wavefront, then the chunks in order): no atomics, two runs are bit-identical.
+ * Refused (non-zero, nothing launched): stages other than 1 / 2, n_frames < 1, n_combos outside 1 .. 108, a frame with a negative
+ * count or more than 1024 GT rows or 1024 detections, a workspace that is too small.  No host synchronisation. */
+int gdmae_kitti_eval_frames_per_chunk(void);
+size_t gdmae_kitti_eval_workspace_bytes(int n_frames, int n_combos);
+int gdmae_kitti_eval(int stages, int n_frames, int n_combos, const int* host_gt_off, const int* host_dt_off, const int* host_dc_off,
+                     const int* gt_off, const int* dt_off, const int* dc_off, const long long* pair_off, const float* gt_box,
+                     const float* gt_geo, const float* gt_alpha, const float* dt_box, const float* dt_geo, const float* dt_alpha,
+                     const float* dt_score, const float* dc_box, const signed char* ignored_gt, const signed char* ignored_dt,
+                     const int* combo_cl, const int* combo_metric, const double* combo_min_overlap, const int* combo_num_gt,
+                     int compute_aos, float* overlaps, float* dc_max, float* matched, const float* sorted_scores, float* thresholds,
+                     int* n_thresholds, long long* pr_counts, double* pr_sim, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
