@@ -626,13 +626,17 @@ def expand_dense(y2, ybg, tiles, a2, b2, B, Y, X):
     output and the border-class constants that ONE DecoderHead call returned (tile-compact on ``tiles``, or dense and None)."""
     R = B * Y * X
     C2 = y2.shape[1]
-    if y2.shape[0] != R and y2.dtype == torch.bfloat16 and C2 % 8 == 0:
+    # a tile-compact Y is the one that came with border-class constants.  Its row count says nothing: with every tile active on a map
+    # of whole tiles it has R rows too, in tile order
+    compact = ybg is not None
+    assert y2.shape[0] == (max(tiles.n_act, 1) * 64 if compact else R), (y2.shape, R, compact)
+    if compact and y2.dtype == torch.bfloat16 and C2 % 8 == 0:
         # tile-compact conv output -> the reference's dense map in one pass (expand + BatchNorm affine + ReLU)
         dmap = torch.empty(R, C2, dtype=torch.float32, device=y2.device)
         L.call("gdmae_tiles_to_dense_affine_relu", L.ptr(y2), L.ptr(tiles.tile_slot), L.ptr(ybg), B, Y, X, C2,
                L.ptr(a2), L.ptr(b2), L.ptr(dmap), L.stream())
         return dmap.view(B, Y, X, -1).permute(0, 3, 1, 2)
-    if y2.shape[0] != R:
+    if compact:
         yd = torch.empty(R, C2, dtype=y2.dtype, device=y2.device)
         L.call("gdmae_tiles_to_dense", L.ptr(y2), L.ptr(tiles.tile_slot), L.ptr(ybg), B, Y, X, C2, y2.element_size(),
                L.ptr(yd), L.stream())
