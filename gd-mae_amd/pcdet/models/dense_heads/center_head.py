@@ -266,12 +266,16 @@ class CenterHead(nn.Module):
             iou = f('iou') if 'iou' in pd else None
             k = min(K, C * H * W)
             score, cell = torch.topk(hm.reshape(B, -1), k)             # best cells over all classes, descending
+            score, cell = score.contiguous(), cell.contiguous()
+            # the fp32 copies are held until the launch is issued: a temporary inside L.ptr(...) goes back to the caching allocator as
+            # soon as its address is taken, and the next map's copy may be written into the same block before the kernel reads it
+            center, center_z, dim, rot = f('center'), f('center_z'), f('dim'), f('rot')
             boxes = torch.empty(B, k, 9 if vel is not None else 7, dtype=torch.float32, device=dev)
             labels = torch.empty(B, k, dtype=torch.int32, device=dev)
             ious = torch.empty(B, k, dtype=torch.float32, device=dev)
             valid = torch.empty(B, k, dtype=torch.uint8, device=dev)
-            L.call("gdmae_center_head_decode", L.ptr(cell.contiguous()), L.ptr(score.contiguous()), L.ptr(f('center')), L.ptr(f('center_z')),
-                   L.ptr(f('dim')), L.ptr(f('rot')), L.ptr(vel), L.ptr(iou), B, k, H, W,
+            L.call("gdmae_center_head_decode", L.ptr(cell), L.ptr(score), L.ptr(center), L.ptr(center_z),
+                   L.ptr(dim), L.ptr(rot), L.ptr(vel), L.ptr(iou), B, k, H, W,
                    L.host_f32([self.point_cloud_range[0], self.point_cloud_range[1]]), L.host_f32([self.voxel_size[0], self.voxel_size[1]]),
                    float(self.feature_map_stride), L.host_f32(list(cfg.POST_CENTER_LIMIT_RANGE)),
                    float(cfg.SCORE_THRESH if cfg.SCORE_THRESH is not None else 0.0), int(cfg.SCORE_THRESH is not None),
@@ -361,14 +365,16 @@ class CenterHead(nn.Module):
         k = min(K, C * H * W)
         n_out = self.batched_rows(C * H * W)
         score, cell = torch.topk(hm.reshape(B, -1), k)
+        score, cell = score.contiguous(), cell.contiguous()
+        center, center_z, dim, rot = f('center'), f('center_z'), f('dim'), f('rot')       # held until the launch (see generate_predicted_boxes)
         bd = 9 if vel is not None else 7
         out = {'pred_boxes': torch.empty(B, n_out, bd, dtype=torch.float32, device=dev),
                'pred_scores': torch.empty(B, n_out, dtype=torch.float32, device=dev),
                'pred_labels': torch.empty(B, n_out, dtype=torch.int64, device=dev),
                'num': torch.empty(B, dtype=torch.int32, device=dev)}
         ws = torch.empty(L.load().gdmae_center_head_detect_workspace_bytes(B, k, bd), dtype=torch.uint8, device=dev)
-        L.call("gdmae_center_head_detect", L.ptr(cell.contiguous()), L.ptr(score.contiguous()), L.ptr(f('center')), L.ptr(f('center_z')),
-               L.ptr(f('dim')), L.ptr(f('rot')), L.ptr(vel), L.ptr(iou), B, k, H, W,
+        L.call("gdmae_center_head_detect", L.ptr(cell), L.ptr(score), L.ptr(center), L.ptr(center_z),
+               L.ptr(dim), L.ptr(rot), L.ptr(vel), L.ptr(iou), B, k, H, W,
                L.host_f32([self.point_cloud_range[0], self.point_cloud_range[1]]), L.host_f32([self.voxel_size[0], self.voxel_size[1]]),
                float(self.feature_map_stride), L.host_f32(list(cfg.POST_CENTER_LIMIT_RANGE)),
                float(cfg.SCORE_THRESH if cfg.SCORE_THRESH is not None else 0.0), int(cfg.SCORE_THRESH is not None),

@@ -470,3 +470,39 @@ def test_graphrcnn_engine_detect_equals_the_engine_call():
         assert torch.equal(out["pred_scores"][b][ok], preds[b]["pred_scores"])
         assert torch.equal(out["pred_labels"][b][ok], preds[b]["pred_labels"])
         assert float(out["pred_boxes"][b][~ok].abs().sum()) == 0 and float(out["pred_scores"][b][~ok].abs().sum()) == 0
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+def test_strided_maps_decode_like_their_contiguous_copies(dtype):
+    """The head's convolutions leave every map as a channel slice of a wider channels-last map (bf16 under autocast), so both tails
+    first make fp32 contiguous copies.  The copies have to live until the launch is issued: taken as temporaries inside the argument
+    list, the copy of `center` went back to the caching allocator once its address was read and the copy of `center_z` was written
+    over it before the kernel ran (with an emptied cache, as here, always; in a long-running process depending on which blocks were
+    free).  Contiguous fp32 maps need no copies: their result is the reference."""
+    head, pd = ts_head(), dense_scene(41, -3.0, 3.0, iou=True).dev()
+    pd = {k: v.to(dtype).float() for k, v in pd.items()}                    # values both dtypes hold exactly
+
+    def strided(m):
+        wide = torch.zeros(m.shape[0], m.shape[2], m.shape[3], 32, dtype=dtype, device=m.device)
+        wide[..., :m.shape[1]] = m.permute(0, 2, 3, 1).to(dtype)
+        v = wide[..., :m.shape[1]].permute(0, 3, 1, 2)
+        assert not v.is_contiguous() and torch.equal(v.float(), m)
+        return v
+
+    views = {k: strided(v) for k, v in pd.items()}
+    Bn = pd["hm"].shape[0]
+    with torch.no_grad():
+        want = head.generate_predicted_boxes(Bn, [pd])
+        want_b = head.generate_predicted_boxes_batched(Bn, [pd])
+        torch.cuda.synchronize()
+        torch.cuda.empty_cache()
+        got = head.generate_predicted_boxes(Bn, [views])
+        torch.cuda.synchronize()
+        torch.cuda.empty_cache()
+        got_b = head.generate_predicted_boxes_batched(Bn, [views])
+    assert sum(w["pred_boxes"].shape[0] for w in want) > 50
+    for b in range(Bn):
+        for k in ("pred_boxes", "pred_scores", "pred_labels"):
+            assert torch.equal(got[b][k], want[b][k]), (b, k)
+    for k in want_b:
+        assert torch.equal(got_b[k], want_b[k]), k
