@@ -19,7 +19,9 @@ The contract, stated once in numpy by ``recall_record_numpy``:
 
 ``update`` sends device tensors to ``gdmae_recall_record`` (csrc/recall_record.hip: two launches, no atomics, no fallback).
 
-The second half of this module is the official KITTI AP table (``kitti_eval``, ``KittiEval``, ``kitti_eval_numpy``)."""
+The second part of this module is the official KITTI AP table (``kitti_eval``, ``KittiEval``, ``kitti_eval_numpy``), the
+third the KITTI annos of the detections on the device (``KittiDetections``, ``kitti_prediction_dicts``, ``evaluate_kitti``,
+``kitti_annos_numpy``)."""
 from __future__ import annotations
 
 import numpy as np
@@ -234,31 +236,50 @@ def kitti_clean_data(gt_annos, dt_annos, classes):
     ignored_dt (C, 3, ND) int8, num_valid (C, 3) int64, dc_rows (NG) bool (``name == "DontCare"``, exact case)."""
     if len(gt_annos) != len(dt_annos):
         raise ValueError(f"kitti_eval: {len(gt_annos)} GT annos and {len(dt_annos)} detection annos")
+    return dict(kitti_clean_gt(gt_annos, classes), **kitti_clean_dt(dt_annos, classes))
+
+
+def _anno_names(annos):
+    return np.concatenate([np.asarray(a['name'], dtype=str).reshape(-1) for a in annos] + [np.zeros(0, dtype=str)])
+
+
+def kitti_clean_gt(gt_annos, classes):
+    """The GT half of ``kitti_clean_data``: gt_off, dc_off, ignored_gt, num_valid, dc_rows."""
     C = len(classes)
-    names = lambda annos: np.concatenate([np.asarray(a['name'], dtype=str).reshape(-1) for a in annos] + [np.zeros(0, dtype=str)])      # noqa: E731
-    gt_raw, dt_raw = names(gt_annos), names(dt_annos)
-    gt_name, dt_name = _LowerNames(gt_raw), _LowerNames(dt_raw)
+    gt_raw = _anno_names(gt_annos)
+    gt_name = _LowerNames(gt_raw)
     gt_count = [len(a['name']) for a in gt_annos]
-    gt_off, dt_off = _offsets(gt_count), _offsets([len(a['name']) for a in dt_annos])
+    gt_off = _offsets(gt_count)
     dc_rows = gt_raw == "DontCare"
     dc_count = np.bincount(np.repeat(np.arange(len(gt_annos)), gt_count)[dc_rows], minlength=len(gt_annos))
-    NG, ND = int(gt_off[-1]), int(dt_off[-1])
+    NG = int(gt_off[-1])
     gt_ignore = _per_row(gt_annos, ('occluded', 'truncated', 'bbox'), (None, None, 4), lambda occ, tr, bb: np.stack(
         [(occ > KITTI_MAX_OCCLUSION[l]) | (tr > KITTI_MAX_TRUNCATION[l]) | ((bb[:, 3] - bb[:, 1]) <= KITTI_MIN_HEIGHT[l]) for l in range(3)]))
-    dt_small = _per_row(dt_annos, ('bbox',), (4,), lambda bb: np.stack([np.abs(bb[:, 3] - bb[:, 1]) < KITTI_MIN_HEIGHT[l] for l in range(3)]))
-    ignored_gt, ignored_dt = np.full((C, 3, NG), -1, np.int8), np.full((C, 3, ND), -1, np.int8)
+    ignored_gt = np.full((C, 3, NG), -1, np.int8)
     for c, cls in enumerate(classes):
         name = KITTI_CLASS_NAMES[cls].lower()
         own = gt_name == name
         neighbour = gt_name == {'pedestrian': 'person_sitting', 'car': 'van'}.get(name, '')       # rows that count as "ignored 1"
-        own_dt = dt_name == name
         for l in range(3):
             ignored_gt[c, l][own & ~gt_ignore[l]] = 0
             ignored_gt[c, l][neighbour | (own & gt_ignore[l])] = 1
+    return dict(gt_off=gt_off, dc_off=_offsets(dc_count), ignored_gt=ignored_gt, num_valid=(ignored_gt == 0).sum(axis=2).astype(np.int64),
+                dc_rows=dc_rows)
+
+
+def kitti_clean_dt(dt_annos, classes):
+    """The detection half of ``kitti_clean_data``: dt_off, ignored_dt (what csrc/kitti_annos.hip decides on the device)."""
+    C = len(classes)
+    dt_name = _LowerNames(_anno_names(dt_annos))
+    dt_off = _offsets([len(a['name']) for a in dt_annos])
+    dt_small = _per_row(dt_annos, ('bbox',), (4,), lambda bb: np.stack([np.abs(bb[:, 3] - bb[:, 1]) < KITTI_MIN_HEIGHT[l] for l in range(3)]))
+    ignored_dt = np.full((C, 3, int(dt_off[-1])), -1, np.int8)
+    for c, cls in enumerate(classes):
+        own_dt = dt_name == KITTI_CLASS_NAMES[cls].lower()
+        for l in range(3):
             ignored_dt[c, l][own_dt] = 0
             ignored_dt[c, l][dt_small[l]] = 1
-    return dict(gt_off=gt_off, dt_off=dt_off, dc_off=_offsets(dc_count), ignored_gt=ignored_gt, ignored_dt=ignored_dt,
-                num_valid=(ignored_gt == 0).sum(axis=2).astype(np.int64), dc_rows=dc_rows)
+    return dict(dt_off=dt_off, ignored_dt=ignored_dt)
 
 
 def kitti_combos(classes, num_valid):
@@ -498,7 +519,8 @@ class KittiEval:
     calls; no host read until ``curves``).  Geometry, boxes, alpha and SCORES are uploaded as fp32: scores are compared as fp32 values
     (two scores that differ only beyond fp32 are a tie, and the lowest detection index wins it, as the reference's strict ``>`` does
     for equal scores); an overlap is an fp32 value that is widened to fp64 against ``min_overlap``.  The per-box flags come from
-    ``kitti_clean_data`` on the host, on the annos' own dtypes."""
+    ``kitti_clean_data`` on the host, on the annos' own dtypes.  ``dt_annos`` may be a ``KittiDetections`` record: the
+    detection arrays and their flags are then the record's device tensors, and the host runs the GT half only."""
 
     def __init__(self, gt_annos, dt_annos, class_names, device="cuda"):
         from . import lib as L
@@ -507,8 +529,18 @@ class KittiEval:
             raise NotImplementedError("kitti_eval: CPU device (the statistics are computed in libgdmae_hip.so, no CPU fallback; "
                                       "kitti_eval_numpy is the CPU path)")
         self.classes = kitti_class_ints(class_names)
-        self.compute_aos = kitti_compute_aos(dt_annos)
-        cd = self.clean = kitti_clean_data(gt_annos, dt_annos, self.classes)
+        record = dt_annos if isinstance(dt_annos, KittiDetections) else None
+        if record is not None:
+            # the detection side stays on the device: the record's tensors, its flags and the host copy of its offsets
+            if len(gt_annos) != record.F:
+                raise ValueError(f"kitti_eval: {len(gt_annos)} GT annos and {record.F} detection frames")
+            device = record.device
+            done = record.finish(self.classes)
+            self.compute_aos = record.compute_aos()
+            cd = self.clean = dict(kitti_clean_gt(gt_annos, self.classes), dt_off=done['dt_off'], ignored_dt=None)
+        else:
+            self.compute_aos = kitti_compute_aos(dt_annos)
+            cd = self.clean = kitti_clean_data(gt_annos, dt_annos, self.classes)
         self.F, self.C = len(gt_annos), len(self.classes)
         go, do = cd['gt_off'], cd['dt_off']
         for what, off in (("GT rows", go), ("detections", do)):
@@ -516,15 +548,22 @@ class KittiEval:
                 raise ValueError(f"kitti_eval: a frame with {int(np.diff(off).max())} {what} (at most {KITTI_MAX_ROWS})")
         self.pair_off = _offsets(np.diff(go) * np.diff(do))
         self.NG, self.ND, self.NP = int(go[-1]), int(do[-1]), int(self.pair_off[-1])
-        gt, dt = kitti_geometry(gt_annos, False), kitti_geometry(dt_annos, True)
+        gt = kitti_geometry(gt_annos, False)
         cl, me, mn, ng = kitti_combos(self.classes, cd['num_valid'])
         self.K = len(cl)
         self._host = [np.ascontiguousarray(o, np.int32) for o in (go, do, cd['dc_off'])]          # kept alive: read by the entry point
         up = lambda a, t: torch.from_numpy(np.ascontiguousarray(a, t)).to(device)      # noqa: E731
         f32 = np.float32
+        if record is not None:
+            dt_side = [done['bbox'], done['geo'], done['alpha'], done['score']]
+            ignored_dt = done['ignored_dt']
+        else:
+            dt = kitti_geometry(dt_annos, True)
+            dt_side = [up(dt['bbox'], f32), up(dt['geo'], f32), up(dt['alpha'], f32), up(dt['score'], f32)]
+            ignored_dt = up(cd['ignored_dt'], np.int8)
         self._in = [up(o, np.int32) for o in self._host] + [up(self.pair_off, np.int64)] + [
-            up(gt['bbox'], f32), up(gt['geo'], f32), up(gt['alpha'], f32), up(dt['bbox'], f32), up(dt['geo'], f32), up(dt['alpha'], f32),
-            up(dt['score'], f32), up(gt['bbox'][cd['dc_rows']], f32), up(cd['ignored_gt'], np.int8), up(cd['ignored_dt'], np.int8),
+            up(gt['bbox'], f32), up(gt['geo'], f32), up(gt['alpha'], f32)] + dt_side + [
+            up(gt['bbox'][cd['dc_rows']], f32), up(cd['ignored_gt'], np.int8), ignored_dt,
             up(cl, np.int32), up(me, np.int32), up(mn, np.float64), up(ng, np.int32)]
         e = lambda *s, dtype=torch.float32: torch.empty(*s, dtype=dtype, device=device)      # noqa: E731
         self._overlaps, self._dc_max, self._matched = e(3, self.NP), e(self.ND), e(self.K, self.NG)
@@ -581,3 +620,376 @@ def kitti_eval(gt_annos, dt_annos, class_names, PR_detail_dict=None, device="cud
     ev = KittiEval(gt_annos, dt_annos, class_names, device)
     precision, _, aos = ev.curves()
     return kitti_format_result(ev.classes, precision, aos, ev.compute_aos, PR_detail_dict)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------
+# KITTI annos of the detections (reference KittiDataset.generate_prediction_dicts)
+#
+#     det = KittiDetections(class_names, device)                      # a padded device store, `rows` rows per frame
+#     for batch_dict in loader:
+#         det.update(engine.detect(batch_dict), batch_dict)           # device copies and one small H2D copy of the calibration
+#     result_str, ret_dict = kitti_eval(gt_annos, det, class_names)   # ONE read of the per-frame counts, ONE gdmae_kitti_annos launch
+#     det.to_annos()                                                  # the reference's list of dicts (one more read)
+# ------------------------------------------------------------------------------------------------------------------------------------
+KITTI_CALIB_FLOATS = 36                # P2 (3, 4), R0 (3, 3), V2C (3, 4), image height, image width, one pad
+KITTI_MAX_NAMES = 16                   # csrc/kitti_annos.hip: entries of the label -> class map
+KITTI_LABEL_LINE = '%s -1 -1 %.4f %.4f %.4f %.4f %.4f %.4f %.4f %.4f %.4f %.4f %.4f %.4f %.4f'
+
+
+def _calib_matrices(calib):
+    """calib: an object with P2 / R0 / V2C (the reference's ``Calibration``) or a dict with P2 / R0 / Tr_velo2cam -> fp32 arrays."""
+    if isinstance(calib, dict):
+        P2, R0, V2C = calib['P2'], calib['R0'], calib['Tr_velo2cam']
+    else:
+        P2, R0, V2C = calib.P2, calib.R0, calib.V2C
+    f = lambda a, s: np.asarray(a, np.float32).reshape(s)      # noqa: E731
+    return f(P2, (3, 4)), f(R0, (3, 3)), f(V2C, (3, 4))
+
+
+def kitti_pack_calib(calib, image_shape=None):
+    """-> (36) fp32, the row of ``gdmae_kitti_annos``; ``image_shape`` = (height, width), zeros when it is filled in on the device"""
+    P2, R0, V2C = _calib_matrices(calib)
+    h, w = (0, 0) if image_shape is None else (int(image_shape[0]), int(image_shape[1]))
+    return np.concatenate([P2.reshape(-1), R0.reshape(-1), V2C.reshape(-1), np.array([h, w, 0], np.float32)]).astype(np.float32)
+
+
+def kitti_annos_template(n=0):
+    """the reference's ``get_template_prediction``"""
+    return {'name': np.zeros(n), 'truncated': np.zeros(n), 'occluded': np.zeros(n), 'alpha': np.zeros(n), 'bbox': np.zeros([n, 4]),
+            'dimensions': np.zeros([n, 3]), 'location': np.zeros([n, 3]), 'rotation_y': np.zeros(n), 'score': np.zeros(n),
+            'boxes_lidar': np.zeros([n, 7])}
+
+
+def _host(t, dtype):
+    return np.asarray(t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else t, dtype)
+
+
+def kitti_annos_numpy(pred_boxes, pred_scores, pred_labels, calib, image_shape, class_names):
+    """The contract of ``gdmae_kitti_annos`` for one sample, stated once: the reference's formulas in fp64 on the fp32 inputs, every
+    result rounded once to fp32.  pred_boxes (n, >= 7) lidar boxes, pred_scores (n), pred_labels (n) 1-based -> the reference's dict.
+    Every sum runs left to right as written (no BLAS), which is the order of csrc/kitti_annos.hip."""
+    boxes = _host(pred_boxes, np.float32)
+    boxes = np.ascontiguousarray(boxes.reshape(-1, boxes.shape[-1] if boxes.ndim == 2 else 7)[:, :7])
+    scores, labels = _host(pred_scores, np.float32).reshape(-1), _host(pred_labels, np.int64).reshape(-1)
+    n = scores.shape[0]
+    if n == 0:
+        return kitti_annos_template(0)
+    P, R, V = (m.astype(np.float64) for m in _calib_matrices(calib))
+    b = boxes.astype(np.float64)
+    x, y, z, l, w, h, heading = (b[:, i] for i in range(7))           # dimensions (dx, dz, dy) are the reference's l, h, w
+    zb = z - h / 2.0
+    cam = [V[i, 0] * x + V[i, 1] * y + V[i, 2] * zb + V[i, 3] for i in range(3)]
+    loc = [R[i, 0] * cam[0] + R[i, 1] * cam[1] + R[i, 2] * cam[2] for i in range(3)]
+    ry = -heading - np.pi / 2.0
+    c, s = np.cos(ry), np.sin(ry)
+    us, vs = [], []
+    with np.errstate(divide='ignore', invalid='ignore'):
+        for k in range(8):
+            xc = (l if (k & 3) < 2 else -l) / 2.0
+            zc = (w if (k & 3) in (0, 3) else -w) / 2.0
+            yc = 0.0 * h if k < 4 else -h
+            X, Y, Z = loc[0] + (xc * c + zc * s), loc[1] + yc, loc[2] + (-xc * s + zc * c)
+            us.append((P[0, 0] * X + P[0, 1] * Y + P[0, 2] * Z + P[0, 3]) / Z)        # divided by the corner's rect z, as the reference does
+            vs.append((P[1, 0] * X + P[1, 1] * Y + P[1, 2] * Z + P[1, 3]) / Z)
+    us, vs = np.stack(us, axis=1), np.stack(vs, axis=1)
+    xmax, ymax = float(int(image_shape[1]) - 1), float(int(image_shape[0]) - 1)
+    clip = lambda v, hi: np.minimum(np.maximum(v, 0.0), hi)      # noqa: E731
+    bbox = np.stack([clip(us.min(axis=1), xmax), clip(vs.min(axis=1), ymax), clip(us.max(axis=1), xmax), clip(vs.max(axis=1), ymax)], axis=1)
+    f32 = np.float32
+    out = kitti_annos_template(n)
+    out['name'] = np.array(class_names)[labels - 1]
+    out['alpha'] = (-np.arctan2(-y, x) + ry).astype(f32)
+    out['bbox'] = bbox.astype(f32)
+    out['dimensions'] = np.stack([boxes[:, 3], boxes[:, 5], boxes[:, 4]], axis=1)
+    out['location'] = np.stack(loc, axis=1).astype(f32)
+    out['rotation_y'] = ry.astype(f32)
+    out['score'] = scores
+    out['boxes_lidar'] = boxes
+    return out
+
+
+def kitti_class_map(class_names):
+    """label - 1 -> KITTI class int as ``kitti_clean_data`` compares names (lower case); -1 for a name that is no KITTI class"""
+    lower = [c.lower() for c in KITTI_CLASS_NAMES]
+    return [lower.index(str(n).lower()) if str(n).lower() in lower else -1 for n in class_names]
+
+
+def kitti_label_lines(anno):
+    """the lines of the reference's label file for one anno dict"""
+    bbox, loc, dims = anno['bbox'], anno['location'], anno['dimensions']
+    return [KITTI_LABEL_LINE % (anno['name'][i], anno['alpha'][i], bbox[i][0], bbox[i][1], bbox[i][2], bbox[i][3], dims[i][1], dims[i][2],
+                                dims[i][0], loc[i][0], loc[i][1], loc[i][2], anno['rotation_y'][i], anno['score'][i]) for i in range(len(bbox))]
+
+
+def _write_label_file(output_path, anno):
+    import os
+    with open(os.path.join(str(output_path), '%s.txt' % anno['frame_id']), 'w') as f:
+        for line in kitti_label_lines(anno):
+            print(line, file=f)
+
+
+def kitti_annos_launch(boxes, scores, labels, num, calib, dt_off, n_det, class_map, classes, out=None):
+    """One ``gdmae_kitti_annos`` launch on device tensors in the layout of ``detect``: boxes (F, rows, >= 7) fp32, scores (F, rows)
+    fp32, labels (F, rows) int64, num (F) int32, calib (F, 36) fp32, dt_off (F + 1) int32 -> dict of the compact outputs (``out``: the
+    tensors to write into).  No host read."""
+    from . import lib as L
+    F, rows, cols = boxes.shape
+    if rows > KITTI_MAX_ROWS or rows < 1:
+        raise ValueError(f"kitti_annos: rows {rows} (1 .. {KITTI_MAX_ROWS})")
+    if not 1 <= len(class_map) <= KITTI_MAX_NAMES or not 1 <= len(classes) <= len(KITTI_CLASS_NAMES):
+        raise ValueError(f"kitti_annos: {len(class_map)} class names (1 .. {KITTI_MAX_NAMES}), {len(classes)} evaluated classes (1 .. 6)")
+    if tuple(scores.shape) != (F, rows) or tuple(labels.shape) != (F, rows) or tuple(num.shape) != (F,) or tuple(calib.shape) != (
+            F, KITTI_CALIB_FLOATS) or tuple(dt_off.shape) != (F + 1,) or cols < 7:
+        raise ValueError("kitti_annos: boxes (F, rows, >= 7), scores / labels (F, rows), num (F), calib (F, 36), dt_off (F + 1)")
+    for t, dtype in ((boxes, torch.float32), (scores, torch.float32), (labels, torch.int64), (num, torch.int32), (calib, torch.float32),
+                     (dt_off, torch.int32)):
+        if t.dtype != dtype or not t.is_cuda:
+            raise ValueError("kitti_annos: fp32 boxes / scores / calib, int64 labels, int32 num / dt_off, all on the device")
+        if not t.is_contiguous():                                                # the entry reads rows of boxes.shape[2] floats
+            raise ValueError("kitti_annos: a tensor that is not contiguous (a column slice of wider boxes, a strided view)")
+    dev, C = boxes.device, len(classes)
+    if out is None:
+        e = lambda *s, dtype=torch.float32: torch.empty(*s, dtype=dtype, device=dev)      # noqa: E731
+        out = dict(bbox=e(n_det, 4), geo=e(n_det, 7), alpha=e(n_det), score=e(n_det), ignored_dt=e(C, 3, n_det, dtype=torch.int8),
+                   boxes_lidar=e(n_det, 7), label=e(n_det, dtype=torch.int32))
+    if F and n_det:
+        with torch.cuda.device(dev):
+            L.call("gdmae_kitti_annos", L.ptr(boxes), cols, L.ptr(scores), L.ptr(labels), L.ptr(num), L.ptr(calib), L.ptr(dt_off), F, rows,
+                   n_det, L.host_i32(class_map), len(class_map), L.host_i32(classes), C, L.ptr(out['bbox']), L.ptr(out['geo']),
+                   L.ptr(out['alpha']), L.ptr(out['score']), L.ptr(out['ignored_dt']), L.ptr(out['boxes_lidar']), L.ptr(out['label']),
+                   L.stream())
+    return out
+
+
+class KittiDetections:
+    """The detections of an evaluation loop as a padded device store (``rows`` rows per frame, grown by doubling) and, after
+    ``finish``, as the compact device tensors ``KittiEval`` reads.  ``update`` makes no host read and no launch of this library;
+    ``finish`` makes the one host read (the per-frame counts) and the one ``gdmae_kitti_annos`` launch."""
+
+    def __init__(self, class_names, device, rows=500, frames=0):
+        self.class_names = [str(c) for c in class_names]
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise NotImplementedError("KittiDetections: CPU device (the annos are computed in libgdmae_hip.so, no CPU fallback; "
+                                      "kitti_annos_numpy is the CPU path)")
+        if not 1 <= rows <= KITTI_MAX_ROWS:
+            raise ValueError(f"KittiDetections: rows {rows} (1 .. {KITTI_MAX_ROWS})")
+        if not 1 <= len(self.class_names) <= KITTI_MAX_NAMES:
+            raise ValueError(f"KittiDetections: {len(self.class_names)} class names (1 .. {KITTI_MAX_NAMES})")
+        self.rows, self.F, self.frame_ids = int(rows), 0, []
+        self.class_map = kitti_class_map(self.class_names)
+        self._cap, self._store, self._pinned = 0, None, []
+        self._host_num = []                      # per update: the counts when the caller knows them on the host, else None
+        self._reserve(int(frames))
+        self._invalidate()
+
+    def _invalidate(self):
+        self._counts, self._first, self._done, self._annos, self._aos = None, None, {}, None, None
+
+    def _reserve(self, need):
+        if need <= self._cap:
+            return
+        cap = self._cap
+        while cap < need:
+            cap = max(2 * cap, 1)
+        e = lambda *s, dtype=torch.float32: torch.empty(*s, dtype=dtype, device=self.device)      # noqa: E731
+        new = dict(boxes=e(cap, self.rows, 7), scores=e(cap, self.rows), labels=e(cap, self.rows, dtype=torch.int64),
+                   num=e(cap, dtype=torch.int32), calib=e(cap, KITTI_CALIB_FLOATS))
+        if self._store is not None and self.F:
+            for k, t in new.items():
+                t[:self.F].copy_(self._store[k][:self.F])
+        self._cap, self._store = cap, new
+
+    def widen(self, rows):
+        """Reallocates the store with ``rows`` (> the present) rows per frame and copies what it holds: device copies, no host read."""
+        if not self.rows < rows <= KITTI_MAX_ROWS:
+            raise ValueError(f"KittiDetections.widen: rows {rows} ({self.rows + 1} .. {KITTI_MAX_ROWS})")
+        old, old_rows = self._store, self.rows
+        self.rows, self._cap, self._store = int(rows), 0, None
+        self._reserve(max(self.F, 1 if old is None else old['num'].shape[0]))
+        if old is not None and self.F:
+            for k in ('boxes', 'scores', 'labels'):
+                self._store[k][:self.F, :old_rows].copy_(old[k][:self.F])
+            for k in ('num', 'calib'):
+                self._store[k][:self.F].copy_(old[k][:self.F])
+        self._invalidate()
+
+    def update(self, out, batch_dict, host_num=None):
+        """out: the padded dict of ``detect`` (pred_boxes (B, n, >= 7), pred_scores (B, n), pred_labels (B, n), num (B)); batch_dict:
+        ``calib`` (B calibrations), ``image_shape`` (B, 2) = (height, width), ``frame_id`` (B).  No host read."""
+        boxes, scores, labels, num = out['pred_boxes'], out['pred_scores'], out['pred_labels'], out['num']
+        if boxes.dim() != 3 or boxes.shape[2] < 7 or tuple(scores.shape) != tuple(boxes.shape[:2]) or tuple(labels.shape) != tuple(
+                boxes.shape[:2]) or tuple(num.shape) != (boxes.shape[0],):
+            raise ValueError("KittiDetections.update: pred_boxes (B, n, >= 7), pred_scores / pred_labels (B, n), num (B)")
+        B, n = scores.shape
+        if n > self.rows:
+            raise ValueError(f"KittiDetections.update: n {n} rows per sample in a store of rows {self.rows}")
+        if not all(t.is_cuda for t in (boxes, scores, labels, num)):
+            raise NotImplementedError("KittiDetections.update: CPU tensors (no CPU fallback; kitti_annos_numpy is the CPU path)")
+        calibs, shapes, ids = batch_dict['calib'], batch_dict['image_shape'], batch_dict['frame_id']
+        if len(calibs) != B or len(shapes) != B or len(ids) != B:
+            raise ValueError(f"KittiDetections.update: {B} samples, {len(calibs)} calibrations, {len(shapes)} image shapes, {len(ids)} frame ids")
+        on_device = isinstance(shapes, torch.Tensor) and shapes.is_cuda          # an image_shape already uploaded is not read back
+        packed = np.stack([kitti_pack_calib(calibs[b], None if on_device else _host(shapes[b], np.int64)) for b in range(B)])
+        self._reserve(self.F + B)
+        s, at = self._store, slice(self.F, self.F + B)
+        if n:
+            s['boxes'][at, :n].copy_(boxes[..., :7])
+            s['scores'][at, :n].copy_(scores)
+            s['labels'][at, :n].copy_(labels)
+        s['num'][at].copy_(num)
+        pinned = torch.from_numpy(packed).pin_memory()                           # one small H2D copy that does not wait for the device
+        s['calib'][at].copy_(pinned, non_blocking=True)
+        self._pinned.append(pinned)                                              # alive until the copy has run (``counts`` waits)
+        if on_device:
+            s['calib'][at, 33:35].copy_(shapes[:, :2])
+        self.frame_ids += list(ids)
+        self._host_num.append(None if host_num is None else [int(v) for v in host_num])
+        self.F += B
+        self._invalidate()
+
+    def _alpha_row(self, row):
+        x, y, heading = float(np.float32(row[0])), float(np.float32(row[1])), float(np.float32(row[6]))
+        return -np.arctan2(-y, x) + (-heading - np.pi / 2.0)
+
+    def counts(self):
+        """(F) int64 per-frame counts on the host: THE host read (cached).  The same read brings the lidar box of the first detection,
+        from which ``compute_aos`` is decided."""
+        if self._counts is None:
+            s, F = self._store, self.F
+            if F == 0:
+                self._counts, self._first = np.zeros(0, np.int64), None
+            elif all(h is not None for h in self._host_num):
+                self._counts = np.array([v for h in self._host_num for v in h], np.int64)
+            else:
+                num = s['num'][:F]
+                first = (num > 0).to(torch.int32).argmax().reshape(1)            # selected on the device: indexing with it would read it
+                packed = torch.cat([num.double(), s['boxes'][:F, 0].index_select(0, first)[0].double()]).cpu().numpy()
+                self._counts = packed[:F].astype(np.int64)
+                self._first = packed[F:]
+                self._pinned = []
+            if self._counts.size and (self._counts.min() < 0 or self._counts.max() > self.rows):
+                raise ValueError(f"KittiDetections: a frame count outside 0 .. {self.rows}")
+        return self._counts
+
+    def finish(self, classes=None):
+        """-> dict: dt_off (F + 1) int64 on the host; on the device bbox (ND, 4), geo (ND, 7), alpha (ND), score (ND), ignored_dt
+        (C, 3, ND) int8 for the evaluated KITTI class ints ``classes`` (default: the record's own names that are KITTI classes),
+        boxes_lidar (ND, 7), label (ND) int32.  Cached per class list until the next ``update``."""
+        if classes is None:
+            classes = [c for c in dict.fromkeys(self.class_map) if c >= 0] or [0]
+        key = tuple(int(c) for c in classes)
+        if key not in self._done:
+            dt_off = _offsets(self.counts())
+            nd = int(dt_off[-1])
+            s, F = self._store, self.F
+            pinned = torch.from_numpy(dt_off.astype(np.int32)).pin_memory()             # an upload that does not wait for the device
+            off_dev = torch.empty(F + 1, dtype=torch.int32, device=self.device)
+            off_dev.copy_(pinned, non_blocking=True)
+            if F:
+                out = kitti_annos_launch(s['boxes'][:F], s['scores'][:F], s['labels'][:F], s['num'][:F], s['calib'][:F], off_dev, nd,
+                                         self.class_map, list(key))
+            else:
+                e = lambda *sh, dtype=torch.float32: torch.empty(*sh, dtype=dtype, device=self.device)      # noqa: E731
+                out = dict(bbox=e(0, 4), geo=e(0, 7), alpha=e(0), score=e(0), ignored_dt=e(len(key), 3, 0, dtype=torch.int8),
+                           boxes_lidar=e(0, 7), label=e(0, dtype=torch.int32))
+            self._done[key] = dict(out, dt_off=dt_off, dt_off_device=off_dev, dt_off_pinned=pinned)
+        return self._done[key]
+
+    def compute_aos(self):
+        """``kitti_compute_aos`` on ``to_annos()``: the first detection's ``alpha != -10``.  Decided on the host from the row that
+        came with the counts (the statement's fp64 value; the device's fp32 value is within an ulp of its rounding), and only when that
+        value is within 1e-5 of -10 by reading the device's own."""
+        if self._aos is None:
+            counts = self.counts()
+            nz = np.nonzero(counts)[0]
+            if nz.size == 0:
+                self._aos = False
+            else:
+                if self._first is None:
+                    self._first = self._store['boxes'][int(nz[0]), 0].double().cpu().numpy()
+                a = self._alpha_row(self._first)
+                self._aos = bool(self.finish()['alpha'][0].item() != -10) if abs(a + 10.0) < 1e-5 else True
+        return self._aos
+
+    def to_annos(self):
+        """The reference's list of anno dicts (fp32 arrays, ``frame_id``; a frame without detections: the empty template).  One more
+        host read (cached)."""
+        if self._annos is None:
+            d = self.finish()
+            off = d['dt_off']
+            flat = torch.cat([d['bbox'], d['geo'], d['alpha'][:, None], d['score'][:, None], d['boxes_lidar'],
+                              d['label'].to(torch.float32)[:, None]], dim=1).cpu().numpy()          # labels are small integers: exact in fp32
+            self._pinned = []
+            label = flat[:, 20].astype(np.int64)
+            names = np.array(self.class_names)
+            annos = []
+            for f in range(self.F):
+                a, b = int(off[f]), int(off[f + 1])
+                anno = kitti_annos_template(b - a)
+                if b > a:
+                    r = flat[a:b]
+                    anno.update(name=names[label[a:b] - 1], alpha=r[:, 11].copy(), bbox=r[:, 0:4].copy(), dimensions=r[:, 7:10].copy(),
+                                location=r[:, 4:7].copy(), rotation_y=r[:, 10].copy(), score=r[:, 12].copy(), boxes_lidar=r[:, 13:20].copy())
+                anno['frame_id'] = self.frame_ids[f]
+                annos.append(anno)
+            self._annos = annos
+        return self._annos
+
+    def write_label_files(self, output_path):
+        """One ``<frame_id>.txt`` per frame in the reference's format."""
+        for anno in self.to_annos():
+            _write_label_file(output_path, anno)
+
+
+def kitti_prediction_dicts(batch_dict, pred_dicts, class_names, output_path=None):
+    """Drop-in for the reference's ``KittiDataset.generate_prediction_dicts``: ``pred_dicts`` is the per-sample list of pred_boxes
+    (n, >= 7), pred_scores (n), pred_labels (n).  Device tensors are padded and go through one ``gdmae_kitti_annos`` launch and one
+    read (the counts are the tensors' shapes); CPU tensors go through ``kitti_annos_numpy``."""
+    if pred_dicts and all(isinstance(d['pred_scores'], torch.Tensor) and d['pred_scores'].is_cuda for d in pred_dicts):
+        counts = [int(d['pred_scores'].shape[0]) for d in pred_dicts]
+        n, B, dev = max(counts), len(pred_dicts), pred_dicts[0]['pred_scores'].device
+        if n > KITTI_MAX_ROWS:
+            raise ValueError(f"kitti_prediction_dicts: a sample with {n} detections (at most {KITTI_MAX_ROWS})")
+        out = {'pred_boxes': torch.zeros(B, n, 7, device=dev), 'pred_scores': torch.zeros(B, n, device=dev),
+               'pred_labels': torch.zeros(B, n, dtype=torch.int64, device=dev), 'num': torch.tensor(counts, dtype=torch.int32).to(dev)}
+        for b, d in enumerate(pred_dicts):
+            if counts[b]:
+                out['pred_boxes'][b, :counts[b]] = d['pred_boxes'][:, :7]
+                out['pred_scores'][b, :counts[b]] = d['pred_scores']
+                out['pred_labels'][b, :counts[b]] = d['pred_labels']
+        det = KittiDetections(class_names, dev, rows=max(n, 1), frames=B)
+        det.update(out, batch_dict, host_num=counts)
+        annos = det.to_annos()
+    else:
+        annos = []
+        for b, d in enumerate(pred_dicts):
+            anno = kitti_annos_numpy(d['pred_boxes'], d['pred_scores'], d['pred_labels'], batch_dict['calib'][b],
+                                     _host(batch_dict['image_shape'][b], np.int64), class_names)
+            anno['frame_id'] = batch_dict['frame_id'][b]
+            annos.append(anno)
+    if output_path is not None:
+        for anno in annos:
+            _write_label_file(output_path, anno)
+    return annos
+
+
+def evaluate_kitti(engine, batches, gt_annos, class_names, keep_annos=False):
+    """The loop of ``evaluate`` with a ``KittiDetections`` record, then ``kitti_eval`` from the record -> (result_str, ret_dict, the
+    reference's anno list or None).  Between ``detect`` and the AP table the host reads the per-frame counts once.  ``engine`` is
+    anything with ``detect(batch_dict)`` (all three engines).  The store starts with 500 rows per frame (KITTI's ``NMS_POST_MAXSIZE``) or
+    the first batch's width if that is larger, and is widened on the device when a later batch is wider; beyond 1024 rows
+    ``KittiDetections`` refuses by name."""
+    det = None
+    for bd in batches:
+        out = engine.detect(bd)
+        n = int(out['pred_scores'].shape[1])
+        if det is None:
+            det = KittiDetections(class_names, out['pred_scores'].device, rows=max(500, n))
+        elif n > det.rows:
+            det.widen(n)
+        det.update(out, bd)
+    if det is None:
+        raise ValueError("evaluate_kitti: no batches")
+    result, ret = kitti_eval(gt_annos, det, class_names)
+    return result, ret, (det.to_annos() if keep_annos else None)

@@ -1114,6 +1114,26 @@ int gdmae_kitti_eval(int stages, int n_frames, int n_combos, const int* host_gt_
                      int compute_aos, float* overlaps, float* dc_max, float* matched, const float* sorted_scores, float* thresholds,
                      int* n_thresholds, long long* pr_counts, double* pr_sim, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- KITTI annos of padded detections (csrc/kitti_annos.hip; KittiDataset.generate_prediction_dicts with
+ * boxes3d_lidar_to_kitti_camera and boxes3d_kitti_camera_to_imageboxes) -------------------------------------------- *
+ * The padded layout of `detect` for n_frames frames: boxes (n_frames, rows, box_stride >= 7) fp32 lidar boxes [x, y, z, dx, dy, dz,
+ * heading, ..] (the first 7 columns of a row are read), scores (n_frames, rows) fp32, labels (n_frames, rows) int64 (1-based), num
+ * (n_frames) int32; rows at or beyond num[f] are not read.  calib (n_frames, 36) fp32 = P2 (3, 4), R0 (3, 3), V2C (3, 4), image
+ * height, image width, one pad.  dt_off (n_frames + 1) int32: the compact row offsets (the running sum of num), n_det = dt_off[n_frames].
+ * All of these on the device.  class_map: n_names (1 .. 16) HOST ints, label - 1 -> KITTI class int (Car 0, Pedestrian 1, Cyclist 2,
+ * Van 3, Person_sitting 4, Truck 5; -1 for any other name); classes: the n_classes (1 .. 6) evaluated KITTI class ints (HOST).
+ * Row `row` < num[f] of frame f writes at o = dt_off[f] + row: bbox (n_det, 4) the clipped image box, geo (n_det, 7) = location (3),
+ * dimensions (dx, dz, dy), rotation_y = -heading - pi / 2, alpha (n_det), score (n_det), boxes_lidar (n_det, 7) and label (n_det)
+ * int32 (copies), ignored_dt (n_classes, 3, n_det) int8: 1 where |bbox height| (fp32, of the rounded box) is under 40 / 25 / 25 px,
+ * else 0 for the row's own class and -1 for any other.  fp64 arithmetic on the fp32 inputs, each result rounded once.
+ * Refused (non-zero, nothing launched): rows outside 1 .. 1024, n_frames < 0, n_det < 0, box_stride < 7, n_names / n_classes out
+ * of range, any null pointer.  n_frames or n_det of 0: nothing is launched.  One launch, no atomics, no workspace, no host
+ * synchronisation. */
+int gdmae_kitti_annos(const float* boxes, int box_stride, const float* scores, const long long* labels, const int* num,
+                      const float* calib, const int* dt_off, int n_frames, int rows, int n_det, const int* class_map, int n_names,
+                      const int* classes, int n_classes, float* bbox, float* geo, float* alpha, float* score,
+                      signed char* ignored_dt, float* boxes_lidar, int* label, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
