@@ -15,7 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.abspath(os.path.join(HERE, "..", "csrc"))
 LIB = os.path.join(CSRC, "libgdmae_hip.so")
 SOURCES = ["capi.hip", "voxelize.hip", "mask.hip", "partition.hip", "segment.hip", "attention.hip", "attention_mfma.hip", "attention_t16.hip", "attention_coop.hip", "layernorm.hip", "decoder.hip", "decoder_blocks.hip", "chamfer.hip",
-           "optim.hip", "input_pipeline.hip", "gemm.hip", "gemm_f32.hip", "encoder_layer.hip", "conv_block.hip", "vfe_fused.hip", "vfe_layer2.hip", "vfe_infer.hip", "conv_tiles.hip", "conv_dense.hip", "tok_gemm.hip", "layer_fused.hip", "rows_gemm.hip", "dw_grouped.hip", "center_head.hip", "center_detect.hip", "anchor_detect.hip", "anchor_head.hip", "anchor_head_infer.hip", "iou3d_nms.hip", "plan.hip", "spconv.hip", "roi_pool.hip", "roi_graph.hip", "gt_sampling.hip", "roi_targets.hip", "recall_record.hip", "kitti_eval.hip", "kitti_annos.hip"]
+           "optim.hip", "input_pipeline.hip", "gemm.hip", "gemm_f32.hip", "encoder_layer.hip", "conv_block.hip", "vfe_fused.hip", "vfe_layer2.hip", "vfe_infer.hip", "conv_tiles.hip", "conv_dense.hip", "tok_gemm.hip", "layer_fused.hip", "rows_gemm.hip", "dw_grouped.hip", "center_head.hip", "center_detect.hip", "anchor_detect.hip", "anchor_head.hip", "anchor_head_infer.hip", "iou3d_nms.hip", "plan.hip", "spconv.hip", "roi_pool.hip", "roi_graph.hip", "gt_sampling.hip", "roi_targets.hip", "recall_record.hip", "kitti_eval.hip", "kitti_annos.hip", "once_eval.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
          "-Wno-unused-result"]
 
@@ -52,6 +52,8 @@ def build(force: bool = False, verbose: bool = True) -> str:
             own = own + [os.path.join(CSRC, "bev_iou.h")]
         if s in ("roi_targets.hip", "recall_record.hip"):
             own = own + [os.path.join(CSRC, "iou3d_rows.h")]
+        if s == "once_eval.hip":
+            own = [os.path.join(CSRC, "rect_clip.h")]
         if s in ("input_pipeline.hip", "gt_sampling.hip"):
             own = own + [os.path.join(CSRC, "aug_xform.h")]
         if force or _newer(src, obj) or any(_newer(d, obj) for d in deps + own):

@@ -21,7 +21,8 @@ The contract, stated once in numpy by ``recall_record_numpy``:
 
 The second part of this module is the official KITTI AP table (``kitti_eval``, ``KittiEval``, ``kitti_eval_numpy``), the
 third the KITTI annos of the detections on the device (``KittiDetections``, ``kitti_prediction_dicts``, ``evaluate_kitti``,
-``kitti_annos_numpy``)."""
+``kitti_annos_numpy``), the fourth the ONCE AP table and its record (``once_eval``, ``OnceEval``, ``once_eval_numpy``,
+``OnceDetections``, ``once_prediction_dicts``, ``evaluate_once``)."""
 from __future__ import annotations
 
 import numpy as np
@@ -993,3 +994,592 @@ def evaluate_kitti(engine, batches, gt_annos, class_names, keep_annos=False):
         raise ValueError("evaluate_kitti: no batches")
     result, ret = kitti_eval(gt_annos, det, class_names)
     return result, ret, (det.to_annos() if keep_annos else None)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------
+# The ONCE AP table (reference pcdet/datasets/once/once_eval/evaluation.py ``get_evaluation_results``)
+#
+#     ret_str, ret_dict = once_eval(gt_annos, pred_annos, classes)                   # libgdmae_hip.so, ONE host read
+#     ret_str, ret_dict = once_eval_numpy(gt_annos, pred_annos, classes)             # the statement: fp64 geometry, numpy, CPU
+#
+# Annos are per-frame dicts: name (n), boxes_3d (n, 7) = (x, y, z, l, w, h, rot) in lidar coordinates, score (n) on the prediction
+# side.  A "combo" is (class, distance band), index class * bands + band.
+# ------------------------------------------------------------------------------------------------------------------------------------
+ONCE_IOU_THRESHOLDS = {'Car': 0.7, 'Bus': 0.7, 'Truck': 0.7, 'Pedestrian': 0.3, 'Cyclist': 0.5}
+ONCE_SUPERCLASS_IOU_THRESHOLDS = {'Vehicle': 0.7, 'Pedestrian': 0.3, 'Cyclist': 0.5}
+ONCE_DIFFICULTY_MODES = {'Overall': ['overall'], 'Distance': ['0-30m', '30-50m', '50m-inf'],
+                         'Overall&Distance': ['overall', '0-30m', '30-50m', '50m-inf']}
+ONCE_MAX_ROWS = 1024                   # predictions / GT rows per frame (csrc/once_eval.hip: 16 mask bits per lane)
+ONCE_MAX_PR_POINTS = 63                # num_pr_points + 1 thresholds, one lane each
+ONCE_THRESHOLD_SLOTS = 64
+ONCE_MAX_CODES = 32                    # name codes: the bits of an accept mask
+ONCE_VEHICLE_NAMES = frozenset(('Car', 'Bus', 'Truck'))
+ONCE_THRESHOLD_EPS = 1e-6              # the slack of the threshold rule's comparison
+
+
+def once_classes(classes, use_superclass):
+    """The evaluated classes: with ``use_superclass`` Car / Bus / Truck (all three, if any) become one leading ``Vehicle``."""
+    if not use_superclass:
+        return list(classes)
+    given = ONCE_VEHICLE_NAMES.intersection(classes)
+    assert not given or given == ONCE_VEHICLE_NAMES, "Car/Bus/Truck must all exist for vehicle detection"      # the reference's message
+    return ['Vehicle'] + [c for c in classes if c not in ONCE_VEHICLE_NAMES]
+
+
+def once_name_codes(classes, use_superclass):
+    """-> (names: code -> name, the LAST code is "any other name"; accept (C) uint32: bit ``code`` set where a row with that code
+    belongs to the evaluated class).  ``Vehicle`` under the superclass rule accepts every code but Pedestrian's and Cyclist's, the
+    "other" code included; every other class accepts its own name only."""
+    names = list(dict.fromkeys(['Pedestrian', 'Cyclist'] + [str(c) for c in classes]))
+    if len(names) + 1 > ONCE_MAX_CODES:
+        raise ValueError(f"once_eval: {len(names)} distinct class names (at most {ONCE_MAX_CODES - 1})")
+    every = (1 << (len(names) + 1)) - 1
+    accept = [every & ~0b11 if (use_superclass and c == 'Vehicle') else 1 << names.index(str(c)) for c in classes]
+    return names, np.array(accept, np.uint32)
+
+
+def _once_names(anno):
+    """the ``name`` column as strings; a zero-row column may be of any dtype (the reference's empty template holds floats)"""
+    name = np.asarray(anno['name']).reshape(-1)
+    return name.astype(str) if name.size else np.zeros(0, dtype='<U1')
+
+
+def once_codes_of(name_lists, names):
+    """per-frame name arrays -> (rows) int32 codes in ``names``, ``len(names)`` for any other name"""
+    flat = np.concatenate([np.zeros(0, dtype='<U1')] + list(name_lists))
+    codes = np.full(flat.shape[0], len(names), np.int32)
+    for i, n in enumerate(names):
+        codes[flat == n] = i
+    return codes
+
+
+def once_boxes(annos):
+    """(rows, 7) fp32: the boxes of all frames as the device compares them"""
+    return _cat([np.asarray(a['boxes_3d']).reshape(-1, 7) for a in annos], 7, np.float32)
+
+
+def once_band_of(boxes):
+    """(n, 7) fp32 -> (n) band: 0 below 30 m, 1 below 50 m, 2 from 50 m, 3 in none; the distance in fp64 on the fp32 values"""
+    b = np.asarray(boxes, np.float32).astype(np.float64)
+    with np.errstate(invalid='ignore'):
+        dist = np.sqrt(b[:, 0] * b[:, 0] + b[:, 1] * b[:, 1] + b[:, 2] * b[:, 2])
+        return np.where(dist < 30, 0, np.where((dist >= 30) & (dist < 50), 1, np.where(dist >= 50, 2, 3))).astype(np.int64)
+
+
+def once_flags(codes, boxes, accept, difficulty_mode):
+    """-> (C, bands, n) int8: 1 outside the band (of ANY class: the reference writes the band after the class), else -1 other class,
+    else 0 accepted"""
+    bands = ONCE_DIFFICULTY_MODES[difficulty_mode]
+    band = once_band_of(boxes)
+    out = np.full((len(accept), len(bands), codes.shape[0]), -1, np.int8)
+    for c, mask in enumerate(accept):
+        own = ((int(mask) >> codes.astype(np.int64)) & 1).astype(bool)
+        for b, tag in enumerate(bands):
+            inside = np.ones_like(own) if tag == 'overall' else band == ('0-30m', '30-50m', '50m-inf').index(tag)
+            out[c, b] = np.where(inside, np.where(own, 0, -1), 1)      # the band is written last in ``filter_data``: it overrides the class
+    return out
+
+
+def once_heading_rejected(rot_gt, rot_pred):
+    """The reference's rule, literally: d = |a - b|, 2 pi - d where d >= pi, rejected where d > pi / 2 (nothing wraps beyond 2 pi)."""
+    d = abs(float(rot_gt) - float(rot_pred))
+    if d >= np.pi:
+        d = 2 * np.pi - d
+    return d > np.pi / 2
+
+
+def once_statement_overlaps(gt, pred, with_heading, bev_overlap):
+    """One frame: gt (G, 7), pred (P, 7) fp32 -> (G, P) fp64 3-D IoU: exact rotated intersection x clipped height overlap over the
+    union; 0 for a pair whose union is 0 and, with the heading rule, for a rejected pair."""
+    g64, p64 = np.asarray(gt, np.float32).astype(np.float64), np.asarray(pred, np.float32).astype(np.float64)
+    out = np.zeros((g64.shape[0], p64.shape[0]), np.float64)
+    turned = lambda b: [b[0], b[1], b[2], b[3], b[4], b[5], -b[6]]      # noqa: E731   rot turns clockwise in (x, y) (the reference's rbbox_to_corners)
+    for i, g in enumerate(g64):
+        for j, p in enumerate(p64):
+            if with_heading and once_heading_rejected(g[6], p[6]):
+                continue
+            ih = min(g[2] + g[5] * 0.5, p[2] + p[5] * 0.5) - max(g[2] - g[5] * 0.5, p[2] - p[5] * 0.5)
+            if not ih > 0:
+                continue
+            inter = bev_overlap(turned(g), turned(p))
+            if not inter > 0:
+                continue
+            i3 = inter * ih
+            union = g[3] * g[4] * g[5] + p[3] * p[4] * p[5] - i3
+            if union != 0:
+                out[i, j] = i3 / union
+    return out
+
+
+def once_overlaps_enough(iou, threshold):
+    """the one comparison of an IoU with its class threshold: strictly above"""
+    return iou > threshold
+
+
+def _once_first_pass(ov, score, flag_gt, flag_pred, min_ov):
+    """``accumulate_scores`` on one frame: ov (G, P) -> the true positives' scores per GT row, -inf elsewhere."""
+    G, P = ov.shape
+    out, assigned = np.full(G, -np.inf, np.float32), np.zeros(P, bool)
+    live = (flag_pred != -1) & (score > -1)                          # the reference's sentinel: a score at or below -1 never matches
+    for g in range(G):
+        if flag_gt[g] == -1:
+            continue
+        cand = live & ~assigned & once_overlaps_enough(ov[g], min_ov)
+        if not cand.any():
+            continue
+        j = int(np.argmax(np.where(cand, score, -np.inf)))          # the highest score; among equal scores the lowest index
+        assigned[j] = True
+        if not (flag_gt[g] == 1 or flag_pred[j] == 1):
+            out[g] = score[j]
+    return out
+
+
+def once_get_thresholds(scores_desc, num_gt, num_pr_points):
+    """The score thresholds of one combo from its true positives' scores in descending order: the fp64 operations of the reference's
+    ``get_thresholds`` in its order (csrc/once_eval.hip ``k_oe_thresholds`` is the same loop).  The true positive of rank r reaches
+    the recall r / num_gt.  A running level climbs in steps of 1 / num_pr_points; a rank is passed over while the middle between its
+    recall and the next rank's is still below the level (the last rank never is), otherwise its score is taken once for the level
+    and again for every further step that stays within ``ONCE_THRESHOLD_EPS`` of that middle.  The count never exceeds
+    ``num_pr_points + 1`` because true positives never outnumber ``num_gt``; a broken bound raises."""
+    step, level, taken, ranks = 1 / num_pr_points, 0, [], len(scores_desc)
+    for rank, score in enumerate(scores_desc, start=1):
+        reached = rank / num_gt
+        twice_middle = ((rank + 1) / num_gt if rank < ranks else reached) + reached
+        if rank < ranks and twice_middle < 2 * level:
+            continue
+        while True:
+            taken.append(score)
+            level += step
+            assert len(taken) <= 4 * (num_pr_points + 1), "once_eval: the threshold rule does not end"
+            if not twice_middle + ONCE_THRESHOLD_EPS > 2 * level:
+                break
+    assert len(taken) <= num_pr_points + 1, f"once_eval: {len(taken)} thresholds for num_pr_points {num_pr_points} (at most num_pr_points + 1)"
+    return taken
+
+
+def once_false_positives(kept, flag_pred, assigned):
+    """kept / assigned (T, P) bool, flag_pred (P) -> (T): the flag-0 predictions at or above the threshold that no GT row took"""
+    return (kept & (flag_pred == 0)[None, :] & ~assigned).sum(axis=1).astype(np.int64)
+
+
+def _once_second_pass(ov, score, flag_gt, flag_pred, min_ov, thresholds):
+    """``compute_statistics`` on one frame for all T thresholds at once -> tp, fp, fn (T) int64.  Per GT row the reference's loop over
+    the predictions ends with the flag-0 candidate of the largest IoU (the first of equals), and only without one with the FIRST
+    flag-1 candidate."""
+    G, P = ov.shape
+    T = len(thresholds)
+    keep = ~(score[None, :] < np.asarray(thresholds, np.float32)[:, None])
+    c0, c1 = keep & (flag_pred == 0)[None, :], keep & (flag_pred == 1)[None, :]
+    assigned = np.zeros((T, P), bool)
+    tp, fn, rows = np.zeros(T, np.int64), np.zeros(T, np.int64), np.arange(T)
+    for g in range(G):
+        if flag_gt[g] == -1:
+            continue
+        if P == 0:
+            fn += int(flag_gt[g] == 0)
+            continue
+        over = once_overlaps_enough(ov[g], min_ov)[None, :]
+        m0 = c0 & ~assigned & over
+        has0 = m0.any(axis=1)
+        j0 = np.argmax(np.where(m0, ov[g][None, :], -1.0), axis=1)
+        m1 = c1 & ~assigned & over
+        has1 = m1.any(axis=1) & ~has0
+        j = np.where(has0, j0, np.argmax(m1, axis=1))
+        found = has0 | has1
+        if flag_gt[g] == 0:
+            fn += ~found
+        assigned[rows[found], j[found]] = True
+        tp += has0 & (flag_gt[g] == 0)
+    return tp, once_false_positives(keep, flag_pred, assigned), fn
+
+
+def once_curves(n_thresholds, counts, n_classes, n_bands, num_pr_points):
+    """(K) counts, (K, >= num_pr_points + 1, 3) tp / fp / fn -> precision, recall, each (C, bands, num_pr_points + 1) fp64: the
+    quotients where a threshold exists, 0 behind the count, then the reverse running maximum over ``th_idx:`` with numpy's 0 / 0."""
+    pts = num_pr_points + 1
+    n_thresholds = np.asarray(n_thresholds).reshape(-1)
+    if n_thresholds.size and int(n_thresholds.max()) > pts:
+        raise AssertionError(f"once_eval: {int(n_thresholds.max())} thresholds for num_pr_points {num_pr_points} (at most num_pr_points + 1)")
+    tp, fp, fn = (np.asarray(counts)[:, :pts, i].astype(np.float64) for i in range(3))
+    mask = np.arange(pts)[None, :] < n_thresholds[:, None]
+    with np.errstate(divide='ignore', invalid='ignore'):
+        curves = [tp / (tp + fp), tp / (tp + fn)]
+    out = []
+    for x in curves:
+        x = np.where(mask, x, 0.0)
+        x = np.maximum.accumulate(x[:, ::-1], axis=1)[:, ::-1]
+        out.append(np.where(mask, x, 0.0).reshape(n_classes, n_bands, pts))
+    return tuple(out)
+
+
+def once_format_result(classes, precision, num_pr_points, difficulty_mode, print_ok=False):
+    """precision (C, bands, num_pr_points + 1) -> (the reference's table text, its ``ret_dict``)"""
+    tags = ONCE_DIFFICULTY_MODES[difficulty_mode]
+    ap = np.zeros(precision.shape[:-1], np.float64)
+    for column in np.moveaxis(precision[..., 1:], -1, 0):             # in index order: the sum is part of the contract's bits
+        ap = ap + column
+    ap = ap / num_pr_points * 100
+    rows = [(str(cls), 'AP_%s' % cls, ap[c]) for c, cls in enumerate(classes)] + [('mAP', 'AP_mean', ap.mean(axis=0))]
+    line = lambda head, cells: "|" + "|".join([head] + cells) + "|\n"      # noqa: E731   every cell is 12 wide, left-aligned
+    text = "\n" + line(f"AP@{str(num_pr_points):<9}", [f"{tag:<12}" for tag in tags])
+    ret = {}
+    for head, key, values in rows:
+        text += line(f"{head:<12}", [f"{v:<12.2f}" for v in values])
+        ret.update({f"{key}/{tag}": v for tag, v in zip(tags, values)})
+    if print_ok:
+        print(text)
+    return text, ret
+
+
+def _once_options(classes, use_superclass, iou_thresholds, num_pr_points, difficulty_mode, n_gt, n_pred):
+    if iou_thresholds is None:
+        iou_thresholds = ONCE_SUPERCLASS_IOU_THRESHOLDS if use_superclass else ONCE_IOU_THRESHOLDS
+    assert n_gt == n_pred, "the number of GT must match predictions"
+    assert difficulty_mode in ONCE_DIFFICULTY_MODES, "difficulty mode is not supported"
+    classes = once_classes(classes, use_superclass)
+    return classes, np.array([float(iou_thresholds[c]) for c in classes], np.float64)
+
+
+def once_eval_numpy(gt_annos, pred_annos, classes, use_superclass=True, iou_thresholds=None, num_pr_points=50,
+                    difficulty_mode='Overall&Distance', ap_with_heading=True, num_parts=100, print_ok=False, stages=False,
+                    bev_overlap=None):
+    """The contract of ``once_eval``, stated once: the reference's steps with fp64 geometry on the fp32 values of the annos
+    (``bev_overlap(a, b)``: the intersection area of two BEV rectangles, default the package's exact convex clipping) and fp32
+    scores.  ``num_parts`` is accepted and ignored.  -> (ret_str, ret_dict), with ``stages`` also a dict of the intermediate results:
+    overlaps (per frame (G, P) fp64), flag_gt (C, bands, NG) / flag_pred (C, bands, ND) int8, num_valid (K), matched (K, NG) fp32,
+    thresholds (K, 64) fp32, n_thresholds (K), counts (K, 64, 3) int64, precision / recall (C, bands, num_pr_points + 1), gt_off,
+    pred_off, classes."""
+    from pcdet.models.roi_heads import proposal_targets as pt
+    bev_overlap = bev_overlap or pt.exact_bev_overlap
+    classes, thr = _once_options(classes, use_superclass, iou_thresholds, num_pr_points, difficulty_mode, len(gt_annos), len(pred_annos))
+    names, accept = once_name_codes(classes, use_superclass)
+    tags = ONCE_DIFFICULTY_MODES[difficulty_mode]
+    F, C, B = len(gt_annos), len(classes), len(tags)
+    gt_names, pred_names = [_once_names(a) for a in gt_annos], [_once_names(a) for a in pred_annos]
+    go, po = _offsets([len(n) for n in gt_names]), _offsets([len(n) for n in pred_names])
+    gt_box, pred_box = once_boxes(gt_annos), once_boxes(pred_annos)
+    score = _cat([a['score'] for a in pred_annos], None, np.float32)
+    flag_gt = once_flags(once_codes_of(gt_names, names), gt_box, accept, difficulty_mode)
+    flag_pred = once_flags(once_codes_of(pred_names, names), pred_box, accept, difficulty_mode)
+    overlaps = [once_statement_overlaps(gt_box[go[f]:go[f + 1]], pred_box[po[f]:po[f + 1]], ap_with_heading, bev_overlap)
+                for f in range(F)]
+    K, NG, slots = C * B, int(go[-1]), ONCE_THRESHOLD_SLOTS
+    fg, fp_ = flag_gt.reshape(K, -1), flag_pred.reshape(K, -1)
+    num_valid = (fg == 0).sum(axis=1).astype(np.int64)
+    matched = np.full((K, NG), -np.inf, np.float32)
+    thresholds, n_thr, counts = np.zeros((K, slots), np.float32), np.zeros(K, np.int64), np.zeros((K, slots, 3), np.int64)
+    for k in range(K):
+        mn = thr[k // B]
+        for f in range(F):
+            matched[k, go[f]:go[f + 1]] = _once_first_pass(overlaps[f], score[po[f]:po[f + 1]], fg[k, go[f]:go[f + 1]],
+                                                           fp_[k, po[f]:po[f + 1]], mn)
+        tps = np.sort(matched[k][matched[k] > -np.inf])[::-1]
+        th = once_get_thresholds(tps, int(num_valid[k]), num_pr_points)
+        n = n_thr[k] = len(th)
+        thresholds[k, :n] = th
+        for f in range(F):
+            tp, fp, fn = _once_second_pass(overlaps[f], score[po[f]:po[f + 1]], fg[k, go[f]:go[f + 1]], fp_[k, po[f]:po[f + 1]], mn, th)
+            counts[k, :n, 0] += tp
+            counts[k, :n, 1] += fp
+            counts[k, :n, 2] += fn
+    precision, recall = once_curves(n_thr, counts, C, B, num_pr_points)
+    ret_str, ret_dict = once_format_result(classes, precision, num_pr_points, difficulty_mode, print_ok)
+    if not stages:
+        return ret_str, ret_dict
+    return ret_str, ret_dict, dict(overlaps=overlaps, flag_gt=flag_gt, flag_pred=flag_pred, num_valid=num_valid, matched=matched,
+                                   thresholds=thresholds, n_thresholds=n_thr, counts=counts, precision=precision, recall=recall, gt_off=go,
+                                   pred_off=po, classes=classes)
+
+
+class OnceEval:
+    """The stages of ``once_eval`` as device tensors (csrc/once_eval.hip: five launches and one ``torch.sort`` between the two calls;
+    no host read until ``curves``).  Boxes and SCORES are uploaded as fp32 and compared as fp32 values; an overlap is an fp32 value
+    that is widened to fp64 against the class threshold.  The host only maps names to codes: the flags are the device's.
+    ``pred_annos`` may be a ``OnceDetections`` record: the prediction side is then the record's device tensors."""
+
+    def __init__(self, gt_annos, pred_annos, classes, device="cuda", use_superclass=True, iou_thresholds=None, num_pr_points=50,
+                 difficulty_mode='Overall&Distance', ap_with_heading=True, num_parts=100, print_ok=False):
+        from . import lib as L
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise NotImplementedError("once_eval: CPU device (the statistics are computed in libgdmae_hip.so, no CPU fallback; "
+                                      "once_eval_numpy is the CPU path)")
+        record = pred_annos if isinstance(pred_annos, OnceDetections) else None
+        n_pred = record.F if record is not None else len(pred_annos)
+        self.classes, thr = _once_options(classes, use_superclass, iou_thresholds, num_pr_points, difficulty_mode, len(gt_annos), n_pred)
+        if not 1 <= int(num_pr_points) <= ONCE_MAX_PR_POINTS:
+            raise ValueError(f"once_eval: num_pr_points {num_pr_points} (1 .. {ONCE_MAX_PR_POINTS}: one lane per threshold)")
+        self.num_pr_points, self.difficulty_mode, self.print_ok = int(num_pr_points), difficulty_mode, print_ok
+        self.names, accept = once_name_codes(self.classes, use_superclass)
+        self.F, self.C, self.B = len(gt_annos), len(self.classes), len(ONCE_DIFFICULTY_MODES[difficulty_mode])
+        self.K = self.C * self.B
+        gt_names = [_once_names(a) for a in gt_annos]
+        go = _offsets([len(n) for n in gt_names])
+        if record is not None:
+            device = record.device
+            po = _offsets(record.counts())
+        else:
+            pred_names = [_once_names(a) for a in pred_annos]
+            po = _offsets([len(n) for n in pred_names])
+        for what, off in (("GT rows", go), ("predictions", po)):
+            if self.F and int(np.diff(off).max()) > ONCE_MAX_ROWS:
+                raise ValueError(f"once_eval: a frame with {int(np.diff(off).max())} {what} (at most {ONCE_MAX_ROWS})")
+        self.gt_off, self.pred_off = go, po
+        self.pair_off = _offsets(np.diff(go) * np.diff(po))
+        self.NG, self.ND, self.NP = int(go[-1]), int(po[-1]), int(self.pair_off[-1])
+        self._host = [np.ascontiguousarray(o, np.int32) for o in (go, po)]                    # kept alive: read by the entry point
+        up = lambda a, t: torch.from_numpy(np.ascontiguousarray(a, t)).to(device)      # noqa: E731
+        if record is not None:
+            pred_side = list(record.compact(self.names))
+        else:
+            pred_side = [up(once_boxes(pred_annos), np.float32), up(_cat([a['score'] for a in pred_annos], None, np.float32), np.float32),
+                         up(once_codes_of(pred_names, self.names), np.int32)]
+        pred_box, pred_score, pred_code = pred_side
+        self._in = [up(o, np.int32) for o in self._host] + [up(self.pair_off, np.int64), up(once_boxes(gt_annos), np.float32), pred_box,
+                                                            pred_score, up(once_codes_of(gt_names, self.names), np.int32), pred_code,
+                                                            up(accept.view(np.int32), np.int32), up(thr, np.float64)]
+        e = lambda *s, dtype=torch.float32: torch.empty(*s, dtype=dtype, device=device)      # noqa: E731
+        slots = ONCE_THRESHOLD_SLOTS
+        self._overlaps, self._matched = e(self.NP), e(self.K, self.NG)
+        self._flag_gt, self._flag_pred = e(self.C, self.B, self.NG, dtype=torch.int8), e(self.C, self.B, self.ND, dtype=torch.int8)
+        self._num_valid, self._thresholds, self._n_thr = e(self.K, dtype=torch.int32), e(self.K, slots), e(self.K, dtype=torch.int32)
+        self._counts = e(self.K, slots, 3, dtype=torch.int64)
+        self._mode = list(ONCE_DIFFICULTY_MODES).index(difficulty_mode)
+        self._heading = int(bool(ap_with_heading))
+        self._curves = None
+        if self.F == 0:                                                     # nothing to launch: no thresholds, every AP is 0
+            self._num_valid.zero_(), self._thresholds.zero_(), self._n_thr.zero_(), self._counts.zero_()
+            self._sorted = self._matched
+            return
+        with torch.cuda.device(device):
+            ws_bytes = L.load().gdmae_once_eval_workspace_bytes(self.F, self.K)
+            ws = e(max(ws_bytes, 1), dtype=torch.uint8)
+            self._call(L, 1, None, None, 0)
+            self._sorted = torch.sort(self._matched, dim=1, descending=True).values.contiguous()
+            self._call(L, 2, self._sorted, ws, ws_bytes)
+
+    def _call(self, L, stage, sorted_scores, ws, ws_bytes):
+        L.call("gdmae_once_eval", stage, self.F, self.C, self._mode, self.num_pr_points, self._heading,
+               *[h.ctypes.data for h in self._host], *[L.ptr(t) for t in self._in], L.ptr(self._overlaps), L.ptr(self._flag_gt),
+               L.ptr(self._flag_pred), L.ptr(self._matched), L.ptr(sorted_scores), L.ptr(self._num_valid), L.ptr(self._thresholds),
+               L.ptr(self._n_thr), L.ptr(self._counts), L.ptr(ws), ws_bytes, L.stream())
+
+    def overlaps(self):
+        """(NP) fp32: the 3-D IoU, per frame GT-major from ``pair_off[f]``.  A device tensor."""
+        return self._overlaps
+
+    def frame_overlaps(self, f):
+        """numpy (G_f, P_f) of frame f, the layout of the statement (a host read: for tests and analysis)."""
+        G, P = int(self.gt_off[f + 1] - self.gt_off[f]), int(self.pred_off[f + 1] - self.pred_off[f])
+        return self._overlaps[int(self.pair_off[f]):int(self.pair_off[f + 1])].cpu().numpy().reshape(G, P)
+
+    def flags(self):
+        """-> (flag_gt (C, bands, NG), flag_pred (C, bands, ND)) int8: 1 outside the band, else -1 other class, else 0 accepted."""
+        return self._flag_gt, self._flag_pred
+
+    def matched_scores(self):
+        """(K, NG) fp32: the score of the first pass's true positive per (combo, GT row), -inf elsewhere."""
+        return self._matched
+
+    def thresholds(self):
+        """-> (thresholds (K, 64) fp32, 0 behind the count; counts (K) int32; num_valid_gt (K) int32)."""
+        return self._thresholds, self._n_thr, self._num_valid
+
+    def counts(self):
+        """(K, 64, 3) int64: tp / fp / fn per (combo, threshold)."""
+        return self._counts
+
+    def curves(self):
+        """-> precision, recall as (C, bands, num_pr_points + 1) fp64 numpy arrays.  The ONE host read (cached)."""
+        if self._curves is None:
+            packed = torch.cat([self._n_thr.to(torch.int64), self._counts.reshape(-1)]).cpu().numpy()
+            self._curves = once_curves(packed[:self.K], packed[self.K:].reshape(self.K, ONCE_THRESHOLD_SLOTS, 3), self.C, self.B,
+                                       self.num_pr_points)
+        return self._curves
+
+    def result(self):
+        """-> (ret_str, ret_dict) of the reference"""
+        return once_format_result(self.classes, self.curves()[0], self.num_pr_points, self.difficulty_mode, self.print_ok)
+
+
+def once_eval(gt_annos, pred_annos, classes, use_superclass=True, iou_thresholds=None, num_pr_points=50,
+              difficulty_mode='Overall&Distance', ap_with_heading=True, num_parts=100, print_ok=False, device="cuda"):
+    """Drop-in for the reference's ``get_evaluation_results`` on the device -> (ret_str, ret_dict).  ``pred_annos``: the
+    reference's list of dicts or a ``OnceDetections`` record."""
+    return OnceEval(gt_annos, pred_annos, classes, device, use_superclass=use_superclass, iou_thresholds=iou_thresholds,
+                    num_pr_points=num_pr_points, difficulty_mode=difficulty_mode, ap_with_heading=ap_with_heading, num_parts=num_parts,
+                    print_ok=print_ok).result()
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------
+# ONCE annos of the detections (reference ONCEDataset.generate_prediction_dicts; DESIGN 7r).  ONCE predictions are the lidar boxes
+# themselves: no kernel of this library, device copies and torch indexing only.
+#
+#     det = OnceDetections(class_names, device)
+#     for batch_dict in loader:
+#         det.update(engine.detect(batch_dict), batch_dict)           # device copies, no host read
+#     ret_str, ret_dict = once_eval(gt_annos, det, class_names)       # ONE read of the per-frame counts, ONE of the counts table
+# ------------------------------------------------------------------------------------------------------------------------------------
+def once_annos_template(n=0):
+    """the reference's ``get_template_prediction``"""
+    return {'name': np.zeros(n), 'score': np.zeros(n), 'boxes_3d': np.zeros((n, 7))}
+
+
+class OnceDetections:
+    """The detections of an evaluation loop as a padded device store (``rows`` rows per frame, frames grown by doubling).  ``update``
+    makes no host read; ``counts`` makes the one host read; ``compact`` and ``to_annos`` index with offsets built on the host."""
+
+    def __init__(self, class_names, device, rows=500, frames=0):
+        self.class_names = [str(c) for c in class_names]
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise NotImplementedError("OnceDetections: CPU device (a device store; once_prediction_dicts is the CPU path)")
+        if not 1 <= rows <= ONCE_MAX_ROWS:
+            raise ValueError(f"OnceDetections: rows {rows} (1 .. {ONCE_MAX_ROWS})")
+        if not self.class_names:
+            raise ValueError("OnceDetections: no class names")
+        self.rows, self.F, self.frame_ids = int(rows), 0, []
+        self._cap, self._store = 0, None
+        self._reserve(int(frames))
+        self._counts = self._annos = self._index = None
+
+    def _reserve(self, need):
+        if need <= self._cap:
+            return
+        cap = self._cap
+        while cap < need:
+            cap = max(2 * cap, 1)
+        e = lambda *s, dtype=torch.float32: torch.zeros(*s, dtype=dtype, device=self.device)      # noqa: E731
+        new = dict(boxes=e(cap, self.rows, 7), scores=e(cap, self.rows), labels=e(cap, self.rows, dtype=torch.int64),
+                   num=e(cap, dtype=torch.int32))
+        if self._store is not None and self.F:
+            for k, t in new.items():
+                t[:self.F].copy_(self._store[k][:self.F])
+        self._cap, self._store = cap, new
+
+    def widen(self, rows):
+        """Reallocates the store with ``rows`` (> the present) rows per frame and copies what it holds: device copies, no host read."""
+        if not self.rows < rows <= ONCE_MAX_ROWS:
+            raise ValueError(f"OnceDetections.widen: rows {rows} ({self.rows + 1} .. {ONCE_MAX_ROWS})")
+        old, old_rows = self._store, self.rows
+        self.rows, self._cap, self._store = int(rows), 0, None
+        self._reserve(max(self.F, 1 if old is None else old['num'].shape[0]))
+        if old is not None and self.F:
+            for k in ('boxes', 'scores', 'labels'):
+                self._store[k][:self.F, :old_rows].copy_(old[k][:self.F])
+            self._store['num'][:self.F].copy_(old['num'][:self.F])
+        self._counts = self._annos = self._index = None
+
+    def update(self, out, batch_dict=None):
+        """out: the padded dict of ``detect`` (pred_boxes (B, n, >= 7), pred_scores (B, n), pred_labels (B, n), num (B)); batch_dict:
+        ``frame_id`` (B), optional.  No host read."""
+        boxes, scores, labels, num = out['pred_boxes'], out['pred_scores'], out['pred_labels'], out['num']
+        if boxes.dim() != 3 or boxes.shape[2] < 7 or tuple(scores.shape) != tuple(boxes.shape[:2]) or tuple(labels.shape) != tuple(
+                boxes.shape[:2]) or tuple(num.shape) != (boxes.shape[0],):
+            raise ValueError("OnceDetections.update: pred_boxes (B, n, >= 7), pred_scores / pred_labels (B, n), num (B)")
+        B, n = scores.shape
+        if n > self.rows:
+            raise ValueError(f"OnceDetections.update: n {n} rows per sample in a store of rows {self.rows}")
+        if not all(t.is_cuda for t in (boxes, scores, labels, num)):
+            raise NotImplementedError("OnceDetections.update: CPU tensors (once_prediction_dicts is the CPU path)")
+        ids = list(batch_dict['frame_id']) if batch_dict is not None and 'frame_id' in batch_dict else list(range(self.F, self.F + B))
+        if len(ids) != B:
+            raise ValueError(f"OnceDetections.update: {B} samples, {len(ids)} frame ids")
+        self._reserve(self.F + B)
+        s, at = self._store, slice(self.F, self.F + B)
+        if n:
+            s['boxes'][at, :n].copy_(boxes[..., :7])
+            s['scores'][at, :n].copy_(scores)
+            s['labels'][at, :n].copy_(labels)
+        s['num'][at].copy_(num)
+        self.frame_ids += ids
+        self.F += B
+        self._counts = self._annos = self._index = None
+
+    def counts(self):
+        """(F) int64 per-frame counts on the host: THE host read (cached until the next ``update``)."""
+        if self._counts is None:
+            self._counts = self._store['num'][:self.F].cpu().numpy().astype(np.int64) if self.F else np.zeros(0, np.int64)
+            if self._counts.size and (self._counts.min() < 0 or self._counts.max() > self.rows):
+                raise ValueError(f"OnceDetections: a frame count outside 0 .. {self.rows}")
+        return self._counts
+
+    def _rows_index(self):
+        """the flat store rows (frame * rows + row) of the compact table, built on the host from the counts and uploaded"""
+        counts = self.counts()
+        if self._index is None:
+            off = _offsets(counts)
+            idx = np.arange(int(off[-1]), dtype=np.int64) - np.repeat(off[:-1], counts) + np.repeat(np.arange(self.F, dtype=np.int64) * self.rows, counts)
+            pinned = torch.from_numpy(idx).pin_memory()                              # an upload that does not wait for the device
+            self._index = (torch.empty(idx.shape[0], dtype=torch.int64, device=self.device).copy_(pinned, non_blocking=True), pinned)
+        return self._index[0]
+
+    def compact(self, names):
+        """-> boxes (ND, 7) fp32, scores (ND) fp32, codes (ND) int32 on the device: the rows below ``num`` of every frame in order, the
+        labels mapped to their codes in ``names`` (``len(names)`` for a name that is not in it).  No host read beyond ``counts``."""
+        idx = self._rows_index()
+        table = torch.tensor([names.index(c) if c in names else len(names) for c in self.class_names], dtype=torch.int32).to(self.device)
+        s, F = self._store, self.F
+        labels = s['labels'][:F].reshape(-1).index_select(0, idx)
+        codes = table.index_select(0, (labels - 1).clamp_(0, len(self.class_names) - 1))
+        return (s['boxes'][:F].reshape(-1, 7).index_select(0, idx).contiguous(), s['scores'][:F].reshape(-1).index_select(0, idx).contiguous(),
+                codes.contiguous())
+
+    def to_annos(self):
+        """The reference's list of dicts: name, score (n) fp32, boxes_3d (n, 7) fp32, frame_id.  One more host read (cached)."""
+        if self._annos is None:
+            off = _offsets(self.counts())
+            idx = self._rows_index()
+            s, F = self._store, self.F
+            flat = torch.cat([s['boxes'][:F].reshape(-1, 7).index_select(0, idx), s['scores'][:F].reshape(-1).index_select(0, idx)[:, None],
+                              s['labels'][:F].reshape(-1).index_select(0, idx).to(torch.float32)[:, None]], dim=1).cpu().numpy()
+            names = np.array(self.class_names)
+            annos = []
+            for f in range(F):
+                r = flat[int(off[f]):int(off[f + 1])]
+                anno = once_annos_template(0)
+                if r.shape[0]:
+                    anno = {'name': names[r[:, 8].astype(np.int64) - 1], 'score': r[:, 7].copy(), 'boxes_3d': r[:, :7].copy()}
+                anno['frame_id'] = self.frame_ids[f]
+                annos.append(anno)
+            self._annos = annos
+        return self._annos
+
+
+def once_prediction_dicts(batch_dict, pred_dicts, class_names, output_path=None):
+    """Drop-in for the reference's ``ONCEDataset.generate_prediction_dicts``: ``pred_dicts`` is the per-sample list of pred_boxes
+    (n, >= 7), pred_scores (n), pred_labels (n) (1-based) -> the list of dicts name / score / boxes_3d (fp32) / frame_id."""
+    if output_path is not None:
+        raise NotImplementedError("once_prediction_dicts: output_path (the reference does not write ONCE result files either)")
+    names = np.array([str(c) for c in class_names])
+    annos = []
+    for b, d in enumerate(pred_dicts):
+        scores = _host(d['pred_scores'], np.float32).reshape(-1)
+        anno = once_annos_template(0)
+        if scores.shape[0]:
+            boxes = _host(d['pred_boxes'], np.float32)
+            anno = {'name': names[_host(d['pred_labels'], np.int64).reshape(-1) - 1], 'score': scores.copy(),
+                    'boxes_3d': np.ascontiguousarray(boxes.reshape(scores.shape[0], -1)[:, :7])}
+        anno['frame_id'] = batch_dict['frame_id'][b]
+        annos.append(anno)
+    return annos
+
+
+def evaluate_once(engine, batches, gt_annos, class_names, keep_annos=False, **options):
+    """The loop of ``evaluate_kitti`` with a ``OnceDetections`` record, then ``once_eval`` from the record -> (ret_str, ret_dict, the
+    reference's anno list or None).  ``options``: those of ``once_eval`` (``use_superclass``, ``iou_thresholds``, ...).  The store
+    starts with 500 rows per frame (ONCE's ``NMS_POST_MAXSIZE``) or the first batch's width if that is larger, and is widened on the
+    device when a later batch is wider; beyond 1024 rows ``OnceDetections`` refuses by name."""
+    det = None
+    for bd in batches:
+        out = engine.detect(bd)
+        n = int(out['pred_scores'].shape[1])
+        if det is None:
+            det = OnceDetections(class_names, out['pred_scores'].device, rows=max(500, n))
+        elif n > det.rows:
+            det.widen(n)
+        det.update(out, bd)
+    if det is None:
+        raise ValueError("evaluate_once: no batches")
+    ret_str, ret_dict = once_eval(gt_annos, det, class_names, **options)
+    return ret_str, ret_dict, (det.to_annos() if keep_annos else None)

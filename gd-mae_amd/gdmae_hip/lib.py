@@ -218,6 +218,9 @@ SIGNATURES = {
     "gdmae_kitti_eval_workspace_bytes": (_Z, [_I, _I]),
     "gdmae_kitti_eval": (_I, [_I, _I, _I] + [_P] * 21 + [_I] + [_P] * 9 + [_Z, _P]),
     "gdmae_kitti_annos": (_I, [_P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "gdmae_once_eval_frames_per_chunk": (_I, []),
+    "gdmae_once_eval_workspace_bytes": (_Z, [_I, _I]),
+    "gdmae_once_eval": (_I, [_I] * 6 + [_P] * 22 + [_Z, _P]),
     "gdmae_roi_graph_folded_floats": (_Z, []),
     "gdmae_roi_graph_packed_bytes": (_Z, []),
     "gdmae_roi_graph_workspace_bytes": (_Z, [_L]),

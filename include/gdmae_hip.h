@@ -1134,6 +1134,37 @@ int gdmae_kitti_annos(const float* boxes, int box_stride, const float* scores, c
                       const int* classes, int n_classes, float* bbox, float* geo, float* alpha, float* score,
                       signed char* ignored_dt, float* boxes_lidar, int* label, void* stream);
 
+/* ---- ONCE AP statistics (csrc/once_eval.hip; once_eval/evaluation.py: compute_iou3d, filter_data, accumulate_scores,
+ * get_thresholds, compute_statistics) --------------------------------------------------------------------------------- *
+ * Frames are concatenated: gt_off / pred_off (n_frames + 1) int32 are the row offsets of the GT and prediction tables, pair_off
+ * (n_frames + 1) int64 the offsets of the per-frame (GT row, prediction) pair blocks; host_gt_off / host_pred_off are HOST copies (the
+ * entry point checks the limits on them before anything is launched).  gt_box (NG, 7) / pred_box (ND, 7) fp32 lidar boxes (x, y, z,
+ * l, w, h, rot), pred_score (ND) fp32, gt_code (NG) / pred_code (ND) int32 name codes 0 .. 31, accept (n_classes) uint32: bit `code`
+ * set where a row of that code belongs to the evaluated class, iou_threshold (n_classes) fp64.  difficulty_mode 0 Overall (1 band),
+ * 1 Distance (3 bands: below 30 m, below 50 m, from 50 m), 2 Overall&Distance (4 bands).  A combination is (class, band), index
+ * class * bands + band.
+ * stages == 1: writes overlaps (pairs) fp32, the 3-D IoU per frame GT-major with the heading rule when with_heading (a pair whose
+ *   union is 0 is 0), flag_gt (n_classes, bands, NG) / flag_pred (n_classes, bands, ND) int8 (1 outside the band whatever the
+ *   class, else -1 other class, else 0 accepted; the distance in fp64 on the fp32 box) and matched (combos, NG) fp32: the score of the first pass's true positive per GT
+ *   row, -inf elsewhere (every slot is written).  Two launches.
+ * stages == 2: sorted_scores (combos, NG) = every row of `matched` in descending order; writes num_valid (combos) int32 (flag-0 GT
+ *   rows), thresholds (combos, 64) fp32 (0 behind the count), n_thresholds (combos) int32 (at most num_pr_points + 1 by the rule; a
+ *   larger count means the rule's bound is broken and is for the caller to refuse) and counts (combos, 64, 3) int64 = tp, fp, fn.
+ *   Three launches; workspace: gdmae_once_eval_workspace_bytes(n_frames, combos) bytes.
+ * Scores and overlaps are compared as fp32 values (an overlap widened to fp64 against the threshold).  Sums over frames run in a
+ * fixed order (gdmae_once_eval_frames_per_chunk frames per wavefront, then the chunks in order): no atomics, two runs are bit-identical.
+ * Refused (non-zero, nothing launched): stages other than 1 / 2, n_frames < 1, n_classes outside 1 .. 32, difficulty_mode outside
+ * 0 .. 2, num_pr_points outside 1 .. 63, a frame with a negative count or more than 1024 rows on a side, a workspace that is too
+ * small.  No host synchronisation. */
+int gdmae_once_eval_frames_per_chunk(void);
+size_t gdmae_once_eval_workspace_bytes(int n_frames, int n_combos);
+int gdmae_once_eval(int stages, int n_frames, int n_classes, int difficulty_mode, int num_pr_points, int with_heading,
+                    const int* host_gt_off, const int* host_pred_off, const int* gt_off, const int* pred_off, const long long* pair_off,
+                    const float* gt_box, const float* pred_box, const float* pred_score, const int* gt_code, const int* pred_code,
+                    const unsigned* accept, const double* iou_threshold, float* overlaps, signed char* flag_gt, signed char* flag_pred,
+                    float* matched, const float* sorted_scores, int* num_valid, float* thresholds, int* n_thresholds, long long* counts,
+                    void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
