@@ -546,8 +546,10 @@ __global__ __launch_bounds__(256) void k_segmax_bn_bwd_v8(const void* __restrict
 }
 
 // Same sums without touching x: at an arg-max with out > 0, out = a x + b exactly as the forward rounded it, so
-// x = (out - b) / a (|a| >= 1e-30; the gather of x through arg stays as the fallback for a dead channel).  Turns
-// 16 M scattered 2-byte reads into one streaming pass over (out, dout).  8 channels per thread.
+// x = (out - b) / a wherever that quotient is well conditioned (below); elsewhere - a dead channel, |a| < 1e-30, or a scale
+// that is small against b - x is gathered through arg.  Turns 16 M scattered 2-byte reads into one streaming pass over
+// (out, dout) for ordinary channels.  8 channels per thread.
+#define GD_SEGMAX_RECON_ULPS 4.f
 template <bool XBF>
 __global__ __launch_bounds__(256) void k_segmax_bwd_stats_v8(const void* __restrict__ x, const float* __restrict__ out,
                                                              const int* __restrict__ arg, const float* __restrict__ dout,
@@ -575,7 +577,11 @@ __global__ __launch_bounds__(256) void k_segmax_bwd_stats_v8(const void* __restr
 #pragma unroll
     for (int j = 0; j < 8; ++j)
       if (ov[j] > 0.f) {
-        const float xv = ia[j] != 0.f ? (ov[j] - bv[j]) * ia[j] : dec_ld<XBF>(x, (long long)arg[q + j] * C + c + j);
+        // out carries half an ulp of |out|, so (out - b) / a is x to within 2^-24 (|b| + |out|) / |a|: taken only where that is a
+        // few roundings of x itself (GD_SEGMAX_RECON_ULPS); a small scale against b cancels, and there x is read through arg
+        const float xr = (ov[j] - bv[j]) * ia[j];
+        const bool recon = ia[j] != 0.f && (fabsf(bv[j]) + ov[j]) * fabsf(ia[j]) <= GD_SEGMAX_RECON_ULPS * fabsf(xr);
+        const float xv = recon ? xr : dec_ld<XBF>(x, (long long)arg[q + j] * C + c + j);
         s0[j] += gv[j];
         s1[j] = fmaf(gv[j], xv, s1[j]);
       }
