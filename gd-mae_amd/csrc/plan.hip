@@ -103,6 +103,7 @@ struct Offsets {
   long long lb_state, counts, points, point_coords, inverse, inverse32, voxel_coords, pillar_cell, pt_off, pillar_pts, point_rank,
       sample_off, pillar_mean, cell2pillar, points_pm, row_pillar, vox_ws, mask, len_keep, tok_pillar;
   long long vis_tok_cell, vis_map;
+  long long vfe_row_tok, vfe_vis_rows, vfe_vis_tok, vfe_tok_row_off;      // -1 unless masked with pillar-major rows
   struct {
     long long tok_cell, map, nbr_subm, nbr_subm_t, nbr_down, nbr_down_t, up_sites, win_ws;
     long long w[2][7];
@@ -114,6 +115,74 @@ struct Offsets {
   StageGeo geo[GDMAE_PLAN_MAX_STAGES];
   long long cap_pts, m_cap, cells;
 };
+
+// ---- the visible pillars' rows for DynVFE (gdmae_vfe_max_layer_vis_*): which pillar-major rows belong to a visible pillar ----------
+// Tokens are in ascending pillar order and a pillar's rows are contiguous, so the compact rows of a token are contiguous too:
+// one exclusive scan of the tokens' point counts (tens of thousands of tokens: ONE workgroup, no look-back state) and one pass over
+// the rows.
+constexpr int kTokScanThreads = 1024, kTokScanItems = 4;
+__global__ __launch_bounds__(kTokScanThreads) void k_vfe_tok_row_off(const int* __restrict__ n_tok_p, const int* __restrict__ tok_pillar,
+                                                                     const int* __restrict__ pt_off, int* __restrict__ tok_row_off,
+                                                                     int* __restrict__ n_rows) {
+  __shared__ int s_wave[kTokScanThreads / 64];
+  const int n = *n_tok_p, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int base = 0;
+  for (int t0 = 0; t0 < n; t0 += kTokScanThreads * kTokScanItems) {
+    const int t = t0 + (int)threadIdx.x * kTokScanItems;
+    int c[kTokScanItems], sum = 0;
+#pragma unroll
+    for (int k = 0; k < kTokScanItems; ++k) {
+      c[k] = 0;
+      if (t + k < n) {
+        const int p = tok_pillar[t + k];
+        c[k] = pt_off[p + 1] - pt_off[p];
+      }
+      sum += c[k];
+    }
+    int incl = sum;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const int o = __shfl_up(incl, d, 64);
+      if (lane >= d) incl += o;
+    }
+    if (lane == 63) s_wave[wave] = incl;
+    __syncthreads();
+    int before = 0, all = 0;
+#pragma unroll
+    for (int w = 0; w < kTokScanThreads / 64; ++w) {
+      before += w < wave ? s_wave[w] : 0;
+      all += s_wave[w];
+    }
+    int run = base + before + incl - sum;
+#pragma unroll
+    for (int k = 0; k < kTokScanItems; ++k) {
+      if (t + k < n) tok_row_off[t + k] = run;
+      run += c[k];
+    }
+    base += all;
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    tok_row_off[n] = base;
+    *n_rows = base;
+  }
+}
+__global__ __launch_bounds__(256) void k_vfe_vis_rows(const int* __restrict__ counts, const int* __restrict__ row_pillar,
+                                                      const int* __restrict__ pillar_cell, const int* __restrict__ map,
+                                                      const int* __restrict__ pt_off, const int* __restrict__ tok_row_off,
+                                                      int* __restrict__ row_tok, int* __restrict__ vis_rows, int* __restrict__ vis_tok) {
+  const int N = counts[0];
+  for (int r = blockIdx.x * 256 + threadIdx.x; r < N; r += gridDim.x * 256) {
+    const int p = row_pillar[r];
+    const int t = map[pillar_cell[p]];
+    row_tok[r] = t;
+    if (t >= 0) {
+      const int rc = tok_row_off[t] + (r - pt_off[p]);
+      vis_rows[rc] = r;
+      vis_tok[rc] = t;
+    }
+  }
+}
 
 int check(const gdmae_plan_params* p) {
   GD_REQUIRE(p != nullptr, "geometry plan: null parameters");
@@ -179,7 +248,8 @@ int layout(const gdmae_plan_params* p, gdmae_plan_buffer* table, int max_entries
   if (O.dec) lb += gd_decoder_tiles_lb_state_bytes(nt);
   O.lb_bytes = lb;
   O.lb_state = L.add("lb_state", lb);
-  O.n_counts = 2 + p->n_stages + 16 * p->n_stages + 1 + 1;     // N, M | tokens per stage | 8 per (stage, shift) | active tiles | visible pillars
+  // N, M | tokens per stage | 8 per (stage, shift) | active tiles | visible pillars | rows of the visible pillars
+  O.n_counts = 2 + p->n_stages + 16 * p->n_stages + 1 + 1 + 1;
   O.counts = L.add("counts", sizeof(int) * O.n_counts);
   // ---- voxelization (capacity = number of input points)
   O.points = L.add("points", sizeof(float) * cap * p->n_cols);
@@ -206,6 +276,14 @@ int layout(const gdmae_plan_params* p, gdmae_plan_buffer* table, int max_entries
   if (p->stride[0] == 2) {
     O.vis_tok_cell = L.add("vis.tok_cell", sizeof(int) * O.m_cap);
     O.vis_map = L.add("vis.map", sizeof(int) * O.cells);
+  }
+  // ---- rows of the visible pillars (DynVFE computes the pillar maximum and its backward for those only)
+  O.vfe_row_tok = O.vfe_vis_rows = O.vfe_vis_tok = O.vfe_tok_row_off = -1;
+  if (p->masked && p->want_pm) {
+    O.vfe_row_tok = L.add("vfe.row_tok", sizeof(int) * cap);
+    O.vfe_vis_rows = L.add("vfe.vis_rows", sizeof(int) * cap);
+    O.vfe_vis_tok = L.add("vfe.vis_tok", sizeof(int) * cap);
+    O.vfe_tok_row_off = L.add("vfe.tok_row_off", sizeof(int) * (O.m_cap + 1));
   }
   // ---- stages
   char nm[40];
@@ -303,6 +381,17 @@ extern "C" int gdmae_geometry_plan(const gdmae_plan_params* p, const float* poin
     int rc = gd_plan_visible_tokens(mask, I(O.cell2pillar), O.cells, I(O.tok_pillar), cur_cell, cur_map, cur_n, lb, st);
     if (rc) return rc;
     lb += gd_plan_scan_state_bytes(O.cells);
+  }
+  if (O.vfe_row_tok >= 0) {
+    // cur_map / cur_n: cell -> token and the number of tokens of the visible set
+    hipLaunchKernelGGL(k_vfe_tok_row_off, dim3(1), dim3(kTokScanThreads), 0, st, (const int*)cur_n, (const int*)I(O.tok_pillar),
+                       (const int*)I(O.pt_off), I(O.vfe_tok_row_off), n_vis + 1);
+    GD_LAUNCH_CHECK();
+    const long long blocks = (O.cap_pts + 255) / 256;
+    hipLaunchKernelGGL(k_vfe_vis_rows, dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(256), 0, st, (const int*)counts,
+                       (const int*)I(O.row_pillar), (const int*)I(O.pillar_cell), (const int*)cur_map, (const int*)I(O.pt_off),
+                       (const int*)I(O.vfe_tok_row_off), I(O.vfe_row_tok), I(O.vfe_vis_rows), I(O.vfe_vis_tok));
+    GD_LAUNCH_CHECK();
   }
   // ---- the stages.  The token sets are a chain (a strided stage's set = a scan over its output cells of the previous map); every
   //      other table of a stage only needs the maps, so after the chain ALL index tables of ALL stages are one launch and the two

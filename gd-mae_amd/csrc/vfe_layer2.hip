@@ -185,9 +185,14 @@ __global__ __launch_bounds__(V2_WAVES * 64) void k_v2_stats(const unsigned short
 // 0, the piece of one that continues behind it to slot 1 (a range inside one pillar: slot 0), and k_v2_max_fix joins the pieces of
 // such a pillar in row order.  arg = row of the maximum (strict >: the first row, i.e. the lowest point id, wins ties - (max value,
 // min row) is associative, so joining pieces in order gives the sequential walk's answer bit for bit).
-template <bool F16>
+// VIS (the pre-training step with a prefetched, masked plan): the walk runs over the COMPACT rows [0, N) of the visible pillars only -
+// compact row rc is y1 row vis_rows[rc], rowpil[rc] is its stage-1 token, out / arg are (tokens, 128).  The rows of a token are
+// contiguous in both row spaces, so the real row k_v2_dydw compares arg against is the compact one plus vis_rows[rc] - rc of any row of
+// the pillar: added where a pillar (or a piece of one) is stored - one more load behind the rarely taken branch, no register per
+// accumulator.
+template <bool F16, bool VIS>
 __global__ __launch_bounds__(V2_WAVES * 64) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_v2_max(const unsigned short* __restrict__ y1, long long N,
-                                                          const void* __restrict__ W, const int* __restrict__ pt_off,
+                                                          const void* __restrict__ W, const int* __restrict__ vis_rows,
                                                           const int* __restrict__ rowpil, int M, const float* __restrict__ ab,
                                                           float* __restrict__ out, int* __restrict__ arg, long long per,
                                                           float* __restrict__ pbest, int* __restrict__ parg) {
@@ -231,7 +236,7 @@ __global__ __launch_bounds__(V2_WAVES * 64) __attribute__((amdgpu_waves_per_eu(3
     const bool live = row < lq1;
     const int rc = live ? row : (lq1 > 0 ? lq1 - 1 : 0);
     pl = rowpil[rc];
-    v2_load_y(y1, rc, live, half, ya);
+    v2_load_y(y1, VIS ? vis_rows[rc] : rc, live, half, ya);
   }
   for (int it = 0; it < iters; ++it) {
     const int qt = q0 + 16 * it;                 // first row of this worker's 16-row slice
@@ -242,7 +247,7 @@ __global__ __launch_bounds__(V2_WAVES * 64) __attribute__((amdgpu_waves_per_eu(3
       live_n = row < lq1;
       const int rc = live_n ? row : (lq1 > 0 ? lq1 - 1 : 0);
       pln = rowpil[rc];
-      v2_load_y_raw(y1, rc, half, yn);
+      v2_load_y_raw(y1, VIS ? vis_rows[rc] : rc, half, yn);
     }
     __builtin_amdgcn_sched_barrier(0);           // the loads go out first
     int prow[16];                                // pillar of each of this worker's rows (uniform within the half-wave)
@@ -268,11 +273,12 @@ __global__ __launch_bounds__(V2_WAVES * 64) __attribute__((amdgpu_waves_per_eu(3
       float* const ob = hp ? pbest : out;
       int* const oa = hp ? parg : arg;
       const long long o0 = (long long)(hp ? wk * 2 : cur_in) * V2_CO;
+      const int ro = VIS ? vis_rows[qt - 1] - (qt - 1) : 0;      // (cur_in >= 0: the worker has walked row qt - 1)
       hp = false;
 #pragma unroll
       for (int b = 0; b < 4; ++b) {
         ob[o0 + 32 * b + n] = best[b];
-        oa[o0 + 32 * b + n] = bi[b];
+        oa[o0 + 32 * b + n] = bi[b] + ro;
       }
     }
 #pragma unroll
@@ -289,11 +295,12 @@ __global__ __launch_bounds__(V2_WAVES * 64) __attribute__((amdgpu_waves_per_eu(3
         float* const ob = hp ? pbest : out;
         int* const oa = hp ? parg : arg;
         const long long o0 = (long long)(hp ? wk * 2 : prow[r]) * V2_CO;
+        const int ro = VIS ? vis_rows[qt + r] - (qt + r) : 0;
         hp = false;
 #pragma unroll
         for (int b = 0; b < 4; ++b) {
           ob[o0 + 32 * b + n] = best[b];
-          oa[o0 + 32 * b + n] = bi[b];
+          oa[o0 + 32 * b + n] = bi[b] + ro;
         }
       }
     }
@@ -305,10 +312,11 @@ __global__ __launch_bounds__(V2_WAVES * 64) __attribute__((amdgpu_waves_per_eu(3
     float* const ob = hp || tail ? pbest : out;
     int* const oa = hp || tail ? parg : arg;
     const long long o0 = (long long)(hp ? wk * 2 : (tail ? wk * 2 + 1 : cur)) * V2_CO;
+    const int ro = VIS ? vis_rows[q1 - 1] - (q1 - 1) : 0;        // (cur >= 0: the range is not empty)
 #pragma unroll
     for (int b = 0; b < 4; ++b) {
       ob[o0 + 32 * b + n] = best[b];
-      oa[o0 + 32 * b + n] = bi[b];
+      oa[o0 + 32 * b + n] = bi[b] + ro;
     }
   }
 }
@@ -397,6 +405,101 @@ __global__ __launch_bounds__(256) void k_v2_gstats(const float* __restrict__ out
   }
 }
 
+// first index i of the ascending a[0 .. n) with a[i] >= key (n if none): 64 probes per round instead of one - three dependent loads
+// for 32 k tokens where a binary search makes fifteen.  Invariant: the answer lies in [lo, lo + len], a[lo + len] >= key (or is the end).
+__device__ __forceinline__ int v2_lower_bound_wave(const int* __restrict__ a, int n, int key, int lane) {
+  int lo = 0, len = n;
+  while (len > 0) {
+    const int step = (len + 63) >> 6, idx = lo + lane * step;
+    const int v = idx < lo + len ? a[idx] : 0x7FFFFFFF;
+    const unsigned long long ge = __ballot(v >= key);
+    const int first = ge ? __ffsll((long long)ge) - 1 : 64;
+    if (first == 0) break;                               // a[lo] >= key
+    const int nlo = lo + (first - 1) * step + 1, nend = lo + first * step < lo + len ? lo + first * step : lo + len;
+    lo = nlo;
+    len = nend - nlo;
+  }
+  return lo;
+}
+
+// k_v2_gstats on the rows of the visible pillars only: out / g / gm are (tokens, 128), tok_pillar (ascending) names each token's
+// pillar.  Same grid, same pillar chunk per workgroup, and a visible pillar p is added by thread-row (p - r0) & 7 in ascending p -
+// the thread and the order that add it in k_v2_gstats.  What that kernel adds for a masked pillar is m = +0 (its gradient row is
+// zero): s + 0 = s and fmaf(0, x, s) = s exactly for finite x (a sum that starts at +0 never becomes -0), so every partial row is the
+// same bits.  Each half-wave finds its tokens among 32 at a time with a ballot and keeps four rows of each array in flight.
+__global__ __launch_bounds__(256) void k_v2_gstats_vis(const float* __restrict__ out, const float* __restrict__ ab,
+                                                       const float* __restrict__ g, long long M, const int* __restrict__ tok_pillar,
+                                                       int n_tok, float* __restrict__ gm, float* __restrict__ part) {
+  __shared__ float sR[8 * 2 * V2_CO];
+  __shared__ int sTok[2];
+  const int tr = threadIdx.x >> 5, l = threadIdx.x & 31, c4 = l * 4;
+  const long long chunk = (M + gridDim.x - 1) / gridDim.x;
+  const long long r0 = blockIdx.x * chunk, r1 = r0 + chunk < M ? r0 + chunk : M;
+  if (threadIdx.x < 128) {                             // waves 0 / 1: first token at or behind r0 / r1
+    const int w = threadIdx.x >> 6;
+    const int t = v2_lower_bound_wave(tok_pillar, n_tok, (int)(w == 0 ? r0 : (r1 > r0 ? r1 : r0)), threadIdx.x & 63);
+    if ((threadIdx.x & 63) == 0) sTok[w] = t;
+  }
+  __syncthreads();
+  const int t0 = sTok[0], t1 = sTok[1];
+  float s0[4] = {0.f, 0.f, 0.f, 0.f}, s1[4] = {0.f, 0.f, 0.f, 0.f};
+  const float4 a4 = *reinterpret_cast<const float4*>(ab + c4), b4 = *reinterpret_cast<const float4*>(ab + V2_CO + c4);
+  const float av[4] = {a4.x, a4.y, a4.z, a4.w}, bv[4] = {b4.x, b4.y, b4.z, b4.w};
+  float ia[4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) ia[e] = av[e] != 0.f ? 1.f / av[e] : 0.f;
+  for (int tb = t0; tb < t1; tb += 32) {
+    const int t = tb + l;
+    const int p = tok_pillar[t < t1 ? t : t1 - 1];
+    const bool mine = t < t1 && ((p - (int)r0) & 7) == tr;
+    const unsigned long long bal = __ballot(mine);
+    unsigned m = (unsigned)(bal >> (32 * (tr & 1)));   // this half-wave's tokens among the 32, ascending
+    while (m) {
+      int tk[4];
+      bool ok[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        ok[u] = m != 0u;
+        tk[u] = ok[u] ? tb + __ffs((int)m) - 1 : tb;   // unconditional loads (a valid row), masked below
+        m &= m - 1u;
+      }
+      float4 ov[4], gv[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        ov[u] = *reinterpret_cast<const float4*>(out + (long long)tk[u] * V2_CO + c4);
+        gv[u] = *reinterpret_cast<const float4*>(g + (long long)tk[u] * V2_CO + c4);
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        if (ok[u]) {
+          const float o[4] = {ov[u].x, ov[u].y, ov[u].z, ov[u].w}, gg[4] = {gv[u].x, gv[u].y, gv[u].z, gv[u].w};
+          float mm[4];
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            mm[e] = o[e] > 0.f ? gg[e] : 0.f;
+            s0[e] += mm[e];
+            s1[e] = fmaf(mm[e], (o[e] - bv[e]) * ia[e], s1[e]);
+          }
+          *reinterpret_cast<float4*>(gm + (long long)tk[u] * V2_CO + c4) = make_float4(mm[0], mm[1], mm[2], mm[3]);
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    sR[(tr * 2 + 0) * V2_CO + c4 + e] = s0[e];
+    sR[(tr * 2 + 1) * V2_CO + c4 + e] = s1[e];
+  }
+  __syncthreads();
+  {
+    const int q = threadIdx.x;   // 256 = 2 * V2_CO: (statistic, channel)
+    float a = 0.f;
+#pragma unroll
+    for (int t = 0; t < 8; ++t) a += sR[t * 2 * V2_CO + q];
+    part[(long long)blockIdx.x * 2 * V2_CO + q] = a;
+  }
+}
+
 // dx of one 32-column block of the tile: dx[row][c] = a dh + c0 + c1 h,  dh = gm[pillar][c] at the arg-max row
 struct V2Coef {
   float a, c0, c1;
@@ -430,7 +533,11 @@ __device__ __forceinline__ f32x16 v2_dx(const f32x16& h, const V2Coef& k, const 
 // partials for the fixed-order reduction.  LDS 49 664 bytes and 159 / 161 registers (bf16 / fp16 rows): three workgroups per CU, the
 // grid k_v2_dw had - with the same tiles per workgroup dW is bit-identical to the two-kernel form.  (64-bit gather addresses in v2_dx
 // cost 9 - 11 registers more: the fp16 instantiation then misses the 168 of three waves per SIMD.)
-template <bool F16>
+// VIS: rowpil holds each row's stage-1 token or -1 (a masked pillar's row) and arg / gm are (tokens, 128).  A masked row gathers at
+// token 0, unconditionally like every other row, and gets dh = 0 with no test of its own: arg of a token only ever names rows of that
+// token's pillar (k_v2_max always picks a row), a masked row is in no visible pillar, so its compare with arg cannot hold.  (A sign
+// test per accumulator register on top of the compare took the kernel to 190 registers: two workgroups per CU.)
+template <bool F16, bool VIS>
 __global__ __launch_bounds__(V2_WAVES * 64) void k_v2_dydw(const unsigned short* __restrict__ y1, long long N,
                                                            const void* __restrict__ W, const int* __restrict__ rowpil,
                                                            const float* __restrict__ ab, const float* __restrict__ c01,
@@ -471,7 +578,7 @@ __global__ __launch_bounds__(V2_WAVES * 64) void k_v2_dydw(const unsigned short*
       }
     int prow[16];
 #pragma unroll
-    for (int r = 0; r < 16; ++r) prow[r] = __shfl(pil, v2_row(r, half), 64);
+    for (int r = 0; r < 16; ++r) prow[r] = __shfl(VIS ? (pil > 0 ? pil : 0) : pil, v2_row(r, half), 64);
     const f32x16 h = v2_h<F16>(ya, sW, n, half, b);
     V2Frag bx[2];                      // dx in bf16: registers [8 kk, 8 kk + 8) of the accumulator layout
     {
@@ -531,7 +638,7 @@ __global__ __launch_bounds__(V2_WAVES * 64) void k_v2_dydw(const unsigned short*
 
 template <typename K>
 int v2_resident_blocks(K kernel, int slot, int cap) {
-  static int cache[6] = {0};
+  static int cache[12] = {0};
   if (cache[slot] == 0) {
     int per_cu = 0, dev = 0;
     hipDeviceProp_t prop;
@@ -577,8 +684,10 @@ extern "C" size_t gdmae_vfe_max_layer_workspace_bytes(void) { return v2_ws_bytes
 // out (M, 128) fp32 = max over the pillar of relu(BatchNorm1d_train(y1 W^T)), arg = row of the maximum (first row on
 // ties = lowest point id); stats / ab / mv as gdmae_bn_fold.
 // *_f16: y1 holds fp16 values (gdmae_vfe_point_layer_fwd with out_bf16 = 2) and W is the fp32 (128, 64) master matrix.
-template <bool F16>
-static int v2_fwd(const void* y1, long long N, const void* W, const int* pillar_pt_off, const int* row_pillar, int M, const float* gamma,
+// VIS (gdmae_vfe_max_layer_vis_*): the statistics still run over all N rows; the maximum walks the Nv compact rows of the visible pillars
+// (pillar_pt_off = vis_rows, row_pillar = vis_tok, M = tokens)
+template <bool F16, bool VIS = false>
+static int v2_fwd(const void* y1, long long N, long long Nv, const void* W, const int* pillar_pt_off, const int* row_pillar, int M, const float* gamma,
                   const float* beta, double eps, double momentum, float* running_mean, float* running_var, long long* num_batches,
                   double* stats, float* ab, float* mv, float* out, int* arg, void* workspace, void* stream) {
   GD_REQUIRE(N > 0 && M > 0, "vfe max layer: no points");
@@ -592,14 +701,14 @@ static int v2_fwd(const void* y1, long long N, const void* W, const int* pillar_
   if (rc) return rc;
   // boundary pieces of k_v2_max: 2 slots x 128 columns x (value, row) per worker, in the partial area (the statistics partials have
   // been consumed by the fold above): V2_MAXW_GRID workgroups x 8 workers x 2 KB = the area's 32 MB
-  const int g2 = v2_grid(N, v2_resident_blocks(k_v2_max<F16>, F16 ? 4 : 1, V2_MAXW_GRID));
-  const long long nwk = (long long)g2 * V2_WAVES * 2, per = (N + nwk - 1) / nwk;
+  const int g2 = v2_grid(Nv, v2_resident_blocks(k_v2_max<F16, VIS>, (VIS ? 6 : 0) + (F16 ? 4 : 1), V2_MAXW_GRID));
+  const long long nwk = (long long)g2 * V2_WAVES * 2, per = (Nv + nwk - 1) / nwk;
   float* const pbest = ws.part;
   int* const parg = (int*)(ws.part + nwk * 2 * V2_CO);
-  hipLaunchKernelGGL(k_v2_max<F16>, dim3(g2), dim3(V2_WAVES * 64), 0, st, (const unsigned short*)y1, N, W, pillar_pt_off, row_pillar, M,
+  hipLaunchKernelGGL((k_v2_max<F16, VIS>), dim3(g2), dim3(V2_WAVES * 64), 0, st, (const unsigned short*)y1, Nv, W, pillar_pt_off, row_pillar, M,
                      (const float*)ab, out, arg, per, pbest, parg);
   GD_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_v2_max_fix, dim3((unsigned)nwk), dim3(V2_CO), 0, st, row_pillar, N, per, (const float*)pbest, (const int*)parg,
+  hipLaunchKernelGGL(k_v2_max_fix, dim3((unsigned)nwk), dim3(V2_CO), 0, st, row_pillar, Nv, per, (const float*)pbest, (const int*)parg,
                      out, arg);
   GD_LAUNCH_CHECK();
   return 0;
@@ -609,7 +718,7 @@ extern "C" int gdmae_vfe_max_layer_fwd(const void* y1, long long N, const void* 
                                        const float* beta, double eps, double momentum, float* running_mean,
                                        float* running_var, long long* num_batches, double* stats, float* ab, float* mv,
                                        float* out, int* arg, void* workspace, void* stream) {
-  return v2_fwd<false>(y1, N, W, pillar_pt_off, row_pillar, M, gamma, beta, eps, momentum, running_mean, running_var, num_batches, stats, ab,
+  return v2_fwd<false>(y1, N, N, W, pillar_pt_off, row_pillar, M, gamma, beta, eps, momentum, running_mean, running_var, num_batches, stats, ab,
                        mv, out, arg, workspace, stream);
 }
 extern "C" int gdmae_vfe_max_layer_fwd_f16(const void* y1, long long N, const float* W, const int* pillar_pt_off,
@@ -617,30 +726,33 @@ extern "C" int gdmae_vfe_max_layer_fwd_f16(const void* y1, long long N, const fl
                                            const float* beta, double eps, double momentum, float* running_mean,
                                            float* running_var, long long* num_batches, double* stats, float* ab, float* mv,
                                            float* out, int* arg, void* workspace, void* stream) {
-  return v2_fwd<true>(y1, N, W, pillar_pt_off, row_pillar, M, gamma, beta, eps, momentum, running_mean, running_var, num_batches, stats, ab,
+  return v2_fwd<true>(y1, N, N, W, pillar_pt_off, row_pillar, M, gamma, beta, eps, momentum, running_mean, running_var, num_batches, stats, ab,
                       mv, out, arg, workspace, stream);
 }
 
 // g (M, 128) fp32: gradient of out.  gm: scratch, M * 128 floats (the masked gradient).  dy1 (N, 64) bf16 is written; dgamma / dbeta / dW (128, 64)
 // fp32 are written, or accumulated into when `accumulate`.
-template <bool F16>
+// VIS (tok_pillar != nullptr): g / out / arg / gm are (n_tok, 128) and row_pillar holds each row's token or -1
+template <bool F16, bool VIS = false>
 static int v2_bwd(const void* y1, long long N, const void* W, const int* row_pillar, int M, const float* gamma, const double* stats,
                   const float* ab, const float* out, const int* arg, const float* g, void* gm, void* dy1, float* dgamma, float* dbeta,
-                  float* dW, int accumulate, void* workspace, void* stream) {
+                  float* dW, int accumulate, void* workspace, void* stream, const int* tok_pillar = nullptr, int n_tok = 0) {
   GD_REQUIRE(N > 0 && M > 0, "vfe max layer: no points");
   GD_REQUIRE(M < (1 << 23), "vfe max layer: the (arg, gm) gathers use 32-bit byte offsets");
+  GD_REQUIRE(!VIS || (tok_pillar != nullptr && n_tok > 0 && n_tok <= M), "vfe max layer: visible pillars");
   hipStream_t st = (hipStream_t)stream;
   const V2Ws ws = v2_ws(workspace);
-  int g0 = (int)(M / 64 > V2_MAX_GRID ? V2_MAX_GRID : (M / 64 > 0 ? M / 64 : 1));
-  hipLaunchKernelGGL(k_v2_gstats, dim3(g0), dim3(256), 0, st, out, ab, g, (long long)M, (float*)gm, ws.part);
+  int g0 = (int)(M / 64 > V2_MAX_GRID ? V2_MAX_GRID : (M / 64 > 0 ? M / 64 : 1));      // (VIS too: the partial rows are those of the full path)
+  if constexpr (VIS) hipLaunchKernelGGL(k_v2_gstats_vis, dim3(g0), dim3(256), 0, st, out, ab, g, (long long)M, tok_pillar, n_tok, (float*)gm, ws.part);
+  else hipLaunchKernelGGL(k_v2_gstats, dim3(g0), dim3(256), 0, st, out, ab, g, (long long)M, (float*)gm, ws.part);
   GD_LAUNCH_CHECK();
   int rc = gd_partials_to_f64(st, ws.part, g0, 2 * V2_CO, ws.sums);
   if (rc) return rc;
   rc = gdmae_bn_bwd_coeffs(ws.sums, 2, stats, ab, gamma, V2_CO, (double)N, nullptr, dgamma, dbeta, accumulate, ws.c01, stream);
   if (rc) return rc;
-  int g2 = v2_resident_blocks(k_v2_dydw<F16>, F16 ? 5 : 2, V2_DW_GRID);   // one tile per workgroup and iteration; one partial tile each
+  int g2 = v2_resident_blocks(k_v2_dydw<F16, VIS>, (VIS ? 6 : 0) + (F16 ? 5 : 2), V2_DW_GRID);   // one tile per workgroup and iteration; one partial tile each
   if (g2 > (N + 31) / 32) g2 = (int)((N + 31) / 32);
-  hipLaunchKernelGGL(k_v2_dydw<F16>, dim3(g2), dim3(V2_WAVES * 64), 0, st, (const unsigned short*)y1, N, W, row_pillar, (const float*)ab,
+  hipLaunchKernelGGL((k_v2_dydw<F16, VIS>), dim3(g2), dim3(V2_WAVES * 64), 0, st, (const unsigned short*)y1, N, W, row_pillar, (const float*)ab,
                      (const float*)ws.c01, arg, (const float*)gm, (unsigned*)dy1, ws.part);
   GD_LAUNCH_CHECK();
   return gd_splitk_acc(st, ws.part, g2, (long long)V2_CO * V2_CI, dW, accumulate);
@@ -658,4 +770,40 @@ extern "C" int gdmae_vfe_max_layer_bwd_f16(const void* y1, long long N, const fl
                                            void* dy1, float* dgamma, float* dbeta, float* dW, int accumulate, void* workspace,
                                            void* stream) {
   return v2_bwd<true>(y1, N, W, row_pillar, M, gamma, stats, ab, out, arg, g, gm, dy1, dgamma, dbeta, dW, accumulate, workspace, stream);
+}
+
+// The same layer when only the visible pillars' features are wanted (pre-training with a prefetched, masked geometry plan: the encoder
+// gathers a quarter of the pillars at a mask ratio of 0.75).  vis_rows (Nv) = the pillar-major rows of the visible pillars, ascending;
+// vis_tok (Nv) = the stage-1 token of each of them; out / arg / g / gm are (n_tok, 128) - arg still holds pillar-major rows;
+// row_tok (N) = token of each row's pillar or -1, tok_pillar (n_tok) ascending.  The statistics, dy1, dW, dgamma and dbeta are those of
+// the entries above bit for bit (given a gradient that is zero at the masked pillars); M = number of ALL pillars.
+extern "C" int gdmae_vfe_max_layer_vis_fwd(const void* y1, long long N, const void* W, const int* vis_rows, const int* vis_tok, long long Nv,
+                                           int n_tok, const float* gamma, const float* beta, double eps, double momentum,
+                                           float* running_mean, float* running_var, long long* num_batches, double* stats, float* ab,
+                                           float* mv, float* out, int* arg, void* workspace, void* stream) {
+  GD_REQUIRE(Nv > 0 && Nv <= N && n_tok > 0, "vfe max layer: no visible rows");
+  return v2_fwd<false, true>(y1, N, Nv, W, vis_rows, vis_tok, n_tok, gamma, beta, eps, momentum, running_mean, running_var, num_batches, stats,
+                             ab, mv, out, arg, workspace, stream);
+}
+extern "C" int gdmae_vfe_max_layer_vis_fwd_f16(const void* y1, long long N, const float* W, const int* vis_rows, const int* vis_tok,
+                                               long long Nv, int n_tok, const float* gamma, const float* beta, double eps, double momentum,
+                                               float* running_mean, float* running_var, long long* num_batches, double* stats, float* ab,
+                                               float* mv, float* out, int* arg, void* workspace, void* stream) {
+  GD_REQUIRE(Nv > 0 && Nv <= N && n_tok > 0, "vfe max layer: no visible rows");
+  return v2_fwd<true, true>(y1, N, Nv, W, vis_rows, vis_tok, n_tok, gamma, beta, eps, momentum, running_mean, running_var, num_batches, stats,
+                            ab, mv, out, arg, workspace, stream);
+}
+extern "C" int gdmae_vfe_max_layer_vis_bwd(const void* y1, long long N, const void* W, const int* row_tok, const int* tok_pillar, int n_tok,
+                                           int M, const float* gamma, const double* stats, const float* ab, const float* out,
+                                           const int* arg, const float* g, void* gm, void* dy1, float* dgamma, float* dbeta, float* dW,
+                                           int accumulate, void* workspace, void* stream) {
+  return v2_bwd<false, true>(y1, N, W, row_tok, M, gamma, stats, ab, out, arg, g, gm, dy1, dgamma, dbeta, dW, accumulate, workspace, stream,
+                             tok_pillar, n_tok);
+}
+extern "C" int gdmae_vfe_max_layer_vis_bwd_f16(const void* y1, long long N, const float* W, const int* row_tok, const int* tok_pillar,
+                                               int n_tok, int M, const float* gamma, const double* stats, const float* ab, const float* out,
+                                               const int* arg, const float* g, void* gm, void* dy1, float* dgamma, float* dbeta, float* dW,
+                                               int accumulate, void* workspace, void* stream) {
+  return v2_bwd<true, true>(y1, N, W, row_tok, M, gamma, stats, ab, out, arg, g, gm, dy1, dgamma, dbeta, dW, accumulate, workspace, stream,
+                            tok_pillar, n_tok);
 }

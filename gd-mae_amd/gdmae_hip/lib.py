@@ -40,6 +40,10 @@ SIGNATURES = {
     "gdmae_vfe_max_layer_bwd": (_I, [_P, _L, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P]),
     "gdmae_vfe_max_layer_fwd_f16": (_I, [_P, _L, _P, _P, _P, _I, _P, _P, _D, _D, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "gdmae_vfe_max_layer_bwd_f16": (_I, [_P, _L, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P]),
+    "gdmae_vfe_max_layer_vis_fwd": (_I, [_P, _L, _P, _P, _P, _L, _I, _P, _P, _D, _D, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "gdmae_vfe_max_layer_vis_fwd_f16": (_I, [_P, _L, _P, _P, _P, _L, _I, _P, _P, _D, _D, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "gdmae_vfe_max_layer_vis_bwd": (_I, [_P, _L, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P]),
+    "gdmae_vfe_max_layer_vis_bwd_f16": (_I, [_P, _L, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P]),
     "gdmae_fill_rows": (_I, [_P, _L, _I, _I, _P, _P]),
     "gdmae_weighted_mean_finish": (_I, [_P, _P, _L, _P, _P]),
     "gdmae_decoder_region_workspace_bytes": (_Z, [_I, _I]),

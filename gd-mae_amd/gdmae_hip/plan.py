@@ -148,11 +148,25 @@ class DecoderTiles:
 
 
 @dataclass
+class VfeVisible:
+    """The pillar-major rows of the visible pillars (masked plans of PlanPrefetch): DynVFE computes the pillar maximum and its backward
+    for those only (gdmae_vfe_max_layer_vis_*).  Tokens are in ascending pillar order, so the rows of a token are contiguous."""
+    n_rows: int                        # Nv
+    row_tok: torch.Tensor              # (N,) int32 stage-1 token of each pillar-major row's pillar / -1
+    vis_rows: torch.Tensor             # (Nv,) int32 pillar-major rows of the visible pillars, ascending
+    vis_tok: torch.Tensor              # (Nv,) int32 token of each of those rows
+    tok_row_off: torch.Tensor          # (n_tok + 1,) int32 first of each token's rows in vis_rows
+    tok_pillar: torch.Tensor           # (n_tok,) int32 = EncoderPlan.tok_pillar
+    n_pillars: int                     # M
+
+
+@dataclass
 class EncoderPlan:
     mask: Optional[torch.Tensor]       # (M,) fp32 0 visible / 1 masked (None when nothing is masked)
     tok_pillar: torch.Tensor           # (M1,) pillar id of each stage-1 token
     stages: List[StagePlan]
     dec_tiles: Optional[DecoderTiles] = None
+    vfe_vis: Optional[VfeVisible] = None   # masked plans of PlanPrefetch only
 
 
 def upsample_cells(c: torch.Tensor, Ys: int, Xs: int, s: int) -> torch.Tensor:
@@ -602,6 +616,10 @@ class PlanPrefetch:
                               nbrs)
         ep = EncoderPlan(V("mask", f32, M) if self.masked else None, V("tok_pillar", i32, stages[0].n_tok if not geo[0]["strided"] else n_vis),
                          stages, dt)
+        if self.masked and A.has("vfe.row_tok"):
+            nt, nv = ep.tok_pillar.numel(), int(c[2 + ns + 16 * ns + 2])
+            ep.vfe_vis = VfeVisible(nv, V("vfe.row_tok", i32, N), V("vfe.vis_rows", i32, nv), V("vfe.vis_tok", i32, nv),
+                                    V("vfe.tok_row_off", i32, nt + 1), ep.tok_pillar, M)
         self.arena = self.points = self.keep = None
         return vox, ep
 

@@ -123,14 +123,15 @@ class _BnChannels:
         self.num_batches_tracked = bn.num_batches_tracked if count_batch else torch.zeros_like(bn.num_batches_tracked)
 
 
-def point_layer2_max(y1, row_pillar, weight, bn, pt_off):
+def point_layer2_max(y1, row_pillar, weight, bn, pt_off, vis=None):
     """PointLayer2Max for 64 -> 128 and - config E's DynVFE (64 -> 256, gd_mae ONCE config) - for wider layers as independent
     128-channel blocks: Linear without bias, BatchNorm and the pillar maximum are all per OUTPUT channel, so block b of the result is
     the fused layer on rows [128 b, 128 b + 128) of the weight / BatchNorm vectors (the recompute-fused kernels of csrc/vfe_layer2.hip
-    are written for 128 outputs); the input gradients of the blocks meet in one pass (ops.FanOut).  -> (M, C) fp32."""
+    are written for 128 outputs); the input gradients of the blocks meet in one pass (ops.FanOut).  -> (M, C) fp32, with ``vis``
+    (plan.VfeVisible) the (n_tok, C) rows of the visible pillars."""
     C = weight.shape[0]
     if C == 128:
-        return PointLayer2Max.apply(y1, row_pillar, weight, bn.weight, bn.bias, bn.eps, pt_off, bn)[0]
+        return PointLayer2Max.apply(y1, row_pillar, weight, bn.weight, bn.bias, bn.eps, pt_off, bn, vis)[0]
     assert C % 128 == 0
     nb = C // 128
     ys = ops.FanOut.apply(y1, nb) if (y1.requires_grad and torch.is_grad_enabled()) else (y1,) * nb
@@ -138,7 +139,7 @@ def point_layer2_max(y1, row_pillar, weight, bn, pt_off):
     for b in range(nb):
         c0, c1 = 128 * b, 128 * (b + 1)
         outs.append(PointLayer2Max.apply(ys[b], row_pillar, weight[c0:c1], bn.weight[c0:c1], bn.bias[c0:c1], bn.eps, pt_off,
-                                         _BnChannels(bn, c0, c1, b == 0))[0])
+                                         _BnChannels(bn, c0, c1, b == 0), vis)[0])
     return torch.cat(outs, dim=1)
 
 
@@ -255,10 +256,13 @@ class PointLayer2Max(torch.autograd.Function):
     """Per-pillar max of relu(BatchNorm1d_train(y1 W^T)) for the last DynVFE layer (64 -> 128, Linear without bias) in
     the bf16 throughput mode, as gdmae_vfe_max_layer_fwd / _bwd (csrc/vfe_layer2.hip): the (N, 128) pre-activation is
     recomputed from y1 in MFMA accumulators, never stored.  y1 (N, 64) bf16 with its rows in pillar-major order and
-    row_pillar (N,) int32 = ``vox.row_pillar`` (PointLayer1(pillar_major=True)).  Returns (out (M, 128) fp32, mean, var)."""
+    row_pillar (N,) int32 = ``vox.row_pillar`` (PointLayer1(pillar_major=True)).  Returns (out (M, 128) fp32, mean, var).
+    ``vis`` (plan.VfeVisible of a masked, prefetched plan): the maximum and its backward for the visible pillars only
+    (gdmae_vfe_max_layer_vis_*) - out is (n_tok, 128), row t the feature of pillar ``vis.tok_pillar[t]``, and the gradient arrives per
+    token; the BatchNorm statistics and every gradient this node returns are bit-identical to the full form's."""
 
     @staticmethod
-    def forward(ctx, y1, row_pillar, weight, gamma, beta, eps, pt_off, bn=None):
+    def forward(ctx, y1, row_pillar, weight, gamma, beta, eps, pt_off, bn=None, vis=None):
         dev = y1.device
         C, K = weight.shape
         assert (C, K) == (128, 64) and y1.dtype in (torch.bfloat16, torch.float16) and y1.is_contiguous() and y1.shape[1] == K
@@ -267,9 +271,13 @@ class PointLayer2Max(torch.autograd.Function):
         f16 = y1.dtype == torch.float16          # fp16 rows (inside PointLayers12Max): the kernels round the fp32 master weights themselves
         wb = weight.detach().contiguous() if f16 else ops.shadow(weight, torch.bfloat16).contiguous()
         assert not f16 or wb.dtype == torch.float32
-        ctx.f16 = f16
-        out = torch.empty(M, C, dtype=torch.float32, device=dev)
-        arg = torch.empty(M, C, dtype=torch.int32, device=dev)
+        ctx.f16, ctx.vis, ctx.M = f16, vis, M
+        n_out = M
+        if vis is not None:
+            n_out = vis.tok_pillar.numel()
+            assert vis.n_pillars == M and vis.row_tok.numel() == n and n_out > 0 and vis.n_rows > 0
+        out = torch.empty(n_out, C, dtype=torch.float32, device=dev)
+        arg = torch.empty(n_out, C, dtype=torch.int32, device=dev)
         stats = torch.empty(2 * C, dtype=torch.float64, device=dev)
         ab = torch.empty(2 * C, dtype=torch.float32, device=dev)
         mv = torch.empty(2 * C, dtype=torch.float32, device=dev)
@@ -278,12 +286,15 @@ class PointLayer2Max(torch.autograd.Function):
         mom = 0.0
         if bn is not None and bn.training and bn.running_mean is not None:
             rm, rv, nb, mom = bn.running_mean, bn.running_var, bn.num_batches_tracked, float(bn.momentum)
-        L.call("gdmae_vfe_max_layer_fwd_f16" if f16 else "gdmae_vfe_max_layer_fwd", L.ptr(y1), n, L.ptr(wb), L.ptr(pt_off), L.ptr(row_pillar), M, L.ptr(gamma),
-               L.ptr(beta), float(eps), mom, L.ptr(rm) if rm is not None else None, L.ptr(rv) if rv is not None else None,
-               L.ptr(nb) if nb is not None else None, L.ptr(stats), L.ptr(ab), L.ptr(mv), L.ptr(out), L.ptr(arg), L.ptr(ws),
-               L.stream())
+        tail = (L.ptr(gamma), L.ptr(beta), float(eps), mom, L.ptr(rm) if rm is not None else None, L.ptr(rv) if rv is not None else None,
+                L.ptr(nb) if nb is not None else None, L.ptr(stats), L.ptr(ab), L.ptr(mv), L.ptr(out), L.ptr(arg), L.ptr(ws), L.stream())
+        if vis is not None:
+            L.call("gdmae_vfe_max_layer_vis_fwd_f16" if f16 else "gdmae_vfe_max_layer_vis_fwd", L.ptr(y1), n, L.ptr(wb), L.ptr(vis.vis_rows),
+                   L.ptr(vis.vis_tok), int(vis.n_rows), n_out, *tail)
+        else:
+            L.call("gdmae_vfe_max_layer_fwd_f16" if f16 else "gdmae_vfe_max_layer_fwd", L.ptr(y1), n, L.ptr(wb), L.ptr(pt_off), L.ptr(row_pillar), M, *tail)
         ctx.ws = ws
-        ctx.save_for_backward(y1, row_pillar, wb, gamma.detach(), stats, ab, out, arg)
+        ctx.save_for_backward(y1, row_pillar if vis is None else vis.row_tok, wb, gamma.detach(), stats, ab, out, arg)
         ctx.direct = (ops.direct_grad(weight), *gbn.direct_pair(gamma, beta))
         mf, vf = mv[:C], mv[C:]
         ctx.mark_non_differentiable(mf, vf)
@@ -293,9 +304,10 @@ class PointLayer2Max(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g, _m, _v):
         if g is None:
-            return (None,) * 8
+            return (None,) * 9
         y1, row_pillar, wb, gamma, stats, ab, out, arg = ctx.saved_tensors
-        n, (M, C) = y1.shape[0], out.shape
+        n, M, C, vis = y1.shape[0], ctx.M, out.shape[1], ctx.vis
+        assert g.shape == out.shape
         g = g.float().contiguous()
         dw, dg, db = ctx.direct
         acc = int(dw is not None and dg is not None and db is not None)
@@ -305,12 +317,16 @@ class PointLayer2Max(torch.autograd.Function):
             dg, db = dgb[:C], dgb[C:]
         gm = torch.empty_like(out)
         dy1 = torch.empty(y1.shape, dtype=torch.bfloat16, device=y1.device)        # gradients stay bf16 (their range is why bf16 exists)
-        L.call("gdmae_vfe_max_layer_bwd_f16" if ctx.f16 else "gdmae_vfe_max_layer_bwd", L.ptr(y1), n, L.ptr(wb), L.ptr(row_pillar), M, L.ptr(gamma), L.ptr(stats), L.ptr(ab),
-               L.ptr(out), L.ptr(arg), L.ptr(g), L.ptr(gm), L.ptr(dy1), L.ptr(dg), L.ptr(db), L.ptr(dw), acc,
-               L.ptr(ctx.ws), L.stream())
+        tail = (L.ptr(gamma), L.ptr(stats), L.ptr(ab), L.ptr(out), L.ptr(arg), L.ptr(g), L.ptr(gm), L.ptr(dy1), L.ptr(dg), L.ptr(db), L.ptr(dw),
+                acc, L.ptr(ctx.ws), L.stream())
+        if vis is not None:       # row_pillar: the rows' tokens
+            L.call("gdmae_vfe_max_layer_vis_bwd_f16" if ctx.f16 else "gdmae_vfe_max_layer_vis_bwd", L.ptr(y1), n, L.ptr(wb), L.ptr(row_pillar),
+                   L.ptr(vis.tok_pillar), out.shape[0], M, *tail)
+        else:
+            L.call("gdmae_vfe_max_layer_bwd_f16" if ctx.f16 else "gdmae_vfe_max_layer_bwd", L.ptr(y1), n, L.ptr(wb), L.ptr(row_pillar), M, *tail)
         if acc:
-            return dy1, None, None, None, None, None, None, None
-        return dy1, None, dw, dg, db, None, None, None
+            return dy1, None, None, None, None, None, None, None, None
+        return dy1, None, dw, dg, db, None, None, None, None
 
 
 
@@ -338,10 +354,11 @@ class PointLayers12Max(torch.autograd.Function):
     rows and of the second layer's weights does not average over a pillar's points; with fp16 (11 significand bits, same bytes, same
     matrix-core rate) DynVFE's share of the small-case loss scatter goes away.  Layers wider than 128 outputs
     (config E: 64 -> 256) run as independent 128-channel blocks whose input gradients meet in one gdmae_sum_bf16 pass.
-    forward(vox, W1, gamma1, beta1, eps1, bn1, W2, gamma2, beta2, eps2, bn2) -> (M, C2) fp32."""
+    forward(vox, W1, gamma1, beta1, eps1, bn1, W2, gamma2, beta2, eps2, bn2, vis=None) -> (M, C2) fp32; with ``vis`` (plan.VfeVisible)
+    the (n_tok, C2) rows of the visible pillars, the gradient per token (PointLayer2Max)."""
 
     @staticmethod
-    def forward(ctx, vox, w1, g1, b1, eps1, bn1, w2, g2, b2, eps2, bn2):
+    def forward(ctx, vox, w1, g1, b1, eps1, bn1, w2, g2, b2, eps2, bn2, vis=None):
         c1 = _StandInCtx()
         y1, _, _ = PointLayer1.forward(c1, vox, w1, g1, b1, eps1, bn1, True, True)
         C2 = w2.shape[0]
@@ -351,10 +368,10 @@ class PointLayers12Max(torch.autograd.Function):
             lo, hi = 128 * blk, 128 * (blk + 1)
             c2 = _StandInCtx()
             if C2 == 128:          # the parameters themselves (not slices of them): their gradients go straight into the flat buffer
-                o, _, _ = PointLayer2Max.forward(c2, y1, vox.row_pillar, w2, g2, b2, eps2, vox.pt_off, bn2)
+                o, _, _ = PointLayer2Max.forward(c2, y1, vox.row_pillar, w2, g2, b2, eps2, vox.pt_off, bn2, vis)
             else:
                 o, _, _ = PointLayer2Max.forward(c2, y1, vox.row_pillar, w2[lo:hi], g2[lo:hi], b2[lo:hi], eps2, vox.pt_off,
-                                                 _BnChannels(bn2, lo, hi, blk == 0))
+                                                 _BnChannels(bn2, lo, hi, blk == 0), vis)
                 # slices of flat-buffer parameters: the block's gradients accumulate into the matching rows of the flat views
                 dwf, dgf, dbf = ops.direct_grad(w2), *gbn.direct_pair(g2, b2)
                 if dwf is not None and dgf is not None and dbf is not None:
@@ -375,7 +392,7 @@ class PointLayers12Max(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         if g is None:
-            return (None,) * 11
+            return (None,) * 12
         sv, pos = ctx.saved_tensors, 0
         c1, c2s = ctx.c1, ctx.c2s
         c1.saved_tensors = sv[pos:pos + ctx.counts[0]]
@@ -398,4 +415,4 @@ class PointLayers12Max(torch.autograd.Function):
         r1 = PointLayer1.backward(c1, dy1, None, None)
         c1.saved_tensors = ()
         cat = (lambda ts: None if acc2 else torch.cat(ts, dim=0))
-        return (None, r1[1], r1[2], r1[3], None, None, cat(dw2), cat(dg2), cat(db2), None, None)
+        return (None, r1[1], r1[2], r1[3], None, None, cat(dw2), cat(dg2), cat(db2), None, None, None)

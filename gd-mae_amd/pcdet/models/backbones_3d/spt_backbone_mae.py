@@ -100,7 +100,15 @@ class SPTBackboneMAE(nn.Module):
                                     dec_sources=self._dec_sources())
         batch_dict['voxel_mae_mask'] = ep.mask
         batch_dict['_gdmae_plan'] = ep
-        x = SparseConvTensor(ops.GatherUnique.apply(all_feat, ep.tok_pillar), ep, 0)
+        tok = batch_dict.pop('_gdmae_tok_features', None)
+        if tok is not None:
+            # DynVFE computed the rows of this plan's stage-1 tokens only (prefetched, masked plan): nothing to gather
+            if tok[1] is not ep:
+                raise RuntimeError("DynVFE's token features belong to another geometry plan than batch_dict['_gdmae_plan']")
+            tok_feat = tok[0]
+        else:
+            tok_feat = ops.GatherUnique.apply(all_feat, ep.tok_pillar)
+        x = SparseConvTensor(tok_feat, ep, 0)
         # data-parallel gradient exchange overlapped with the backward (gdmae_hip.optim.GradSync): when autograd delivers
         # the gradient of a stage's INPUT, that stage (and everything after it) has finished its weight gradients
         sync = batch_dict.get('_gdmae_grad_sync', None)

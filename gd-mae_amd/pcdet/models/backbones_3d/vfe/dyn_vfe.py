@@ -23,6 +23,9 @@ class DynVFE(VFETemplate):
     fused = True      # fused BN+ReLU(+max) row kernels; False = torch BatchNorm1d / ReLU modules + segment max
     point_layer = os.environ.get("GDMAE_VFE_POINT_LAYER", "1") != "0"    # first layer as gdmae_vfe_point_layer_*
     max_layer = os.environ.get("GDMAE_VFE_MAX_LAYER", "1") != "0"        # last layer as gdmae_vfe_max_layer_* (bf16 mode)
+    # pillar maximum and its backward for the VISIBLE pillars only when the batch comes with a prefetched, masked plan (round 13);
+    # 0: every pillar, the encoder gathers its tokens (A/B reference in the same library, tools/ab_env.sh)
+    visible_only = os.environ.get("GDMAE_VFE_VISIBLE", "1") != "0"
 
     def __init__(self, model_cfg, num_point_features, voxel_size, point_cloud_range, grid_size, **kwargs):
         super().__init__(model_cfg=model_cfg)
@@ -48,6 +51,7 @@ class DynVFE(VFETemplate):
             vox = gplan.voxelize(batch_dict['points'], self.point_cloud_range, self.voxel_size, self.grid_size,
                                  int(batch_dict['batch_size']))
         mlp = self.dvfe_mlps[0]
+        ep = vis = None
         if self.fused and self.training:
             nl = len(mlp) // 3
             # first layer: decoration + Linear + BatchNorm + ReLU in one call, nothing but its output stored
@@ -58,10 +62,19 @@ class DynVFE(VFETemplate):
             last = (first and self.max_layer and nl == 2 and torch.is_autocast_enabled() and mlp[3].bias is None
                     and mlp[3].weight.shape[1] == 64 and mlp[3].weight.shape[0] in (128, 256) and vox.points_pm is not None)
             x = None if first else ops.decorate_points(vox)
+            # the encoder reads the visible pillars only: with the mask known before this layer runs (a prefetched plan) the pillar
+            # maximum, its arg-max and every gradient row exist per stage-1 token
+            ep = batch_dict.get('_gdmae_plan', None)
+            vis = getattr(ep, 'vfe_vis', None) if (first and last and self.visible_only) else None
+            if vis is not None and (ep.mask is None or vis.tok_pillar.numel() == 0 or vis.n_rows == 0):
+                vis = None
+            if vis is not None:
+                assert vis.n_pillars == vox.M and vis.row_tok.numel() == vox.N, "the plan in the batch belongs to other points"
             if first and last and VFE_F16:
                 # both layers as one autograd node with fp16 rows between them (gdmae_hip.vfe.PointLayers12Max, round 6)
                 l1, bn1, l2, bn2 = mlp[0], mlp[1], mlp[3], mlp[4]
-                x = gvfe.PointLayers12Max.apply(vox, l1.weight, bn1.weight, bn1.bias, bn1.eps, bn1, l2.weight, bn2.weight, bn2.bias, bn2.eps, bn2)
+                x = gvfe.PointLayers12Max.apply(vox, l1.weight, bn1.weight, bn1.bias, bn1.eps, bn1, l2.weight, bn2.weight, bn2.bias, bn2.eps, bn2,
+                                                vis)
                 nl = 0
             for k in range(nl):
                 lin, bn = mlp[3 * k], mlp[3 * k + 1]
@@ -69,7 +82,7 @@ class DynVFE(VFETemplate):
                     x, _, _ = gvfe.PointLayer1.apply(vox, lin.weight, bn.weight, bn.bias, bn.eps, bn, last)
                     continue
                 if k == nl - 1 and last:
-                    x = gvfe.point_layer2_max(x, vox.row_pillar, lin.weight, bn, vox.pt_off)
+                    x = gvfe.point_layer2_max(x, vox.row_pillar, lin.weight, bn, vox.pt_off, vis)
                     continue
                 x = ops.linear(x, lin.weight, lin.bias)
                 if k < nl - 1:
@@ -85,4 +98,9 @@ class DynVFE(VFETemplate):
         batch_dict.update({'points': vox.points, 'point_coords': vox.point_coords,
                            'point_inverse_indices': vox.inverse, 'voxel_coords': vox.voxel_coords,
                            'pillar_features': x, 'voxel_features': x, '_gdmae_vox': vox})
+        batch_dict.pop('_gdmae_tok_features', None)
+        if vis is not None:
+            # x holds the rows of the plan's stage-1 tokens, not of the pillars: published under a name of its own, and the per-pillar
+            # entries are None so that a reader that expects (M, C) rows fails loudly
+            batch_dict.update({'_gdmae_tok_features': (x, ep), 'pillar_features': None, 'voxel_features': None})
         return batch_dict

@@ -132,6 +132,28 @@ int gdmae_vfe_max_layer_bwd_f16(const void* y1, long long N, const float* W, con
                                 const double* stats, const float* ab, const float* out, const int* arg, const float* g, void* gm,
                                 void* dy1, float* dgamma, float* dbeta, float* dW, int accumulate,
                                 void* workspace, void* stream);
+/* Round 13, the same layer for the visible pillars only (pre-training with a masked geometry plan: the encoder reads a quarter of the
+ * pillars at a mask ratio of 0.75).  The BatchNorm statistics, dy1, dW, dgamma and dbeta still cover all N rows and are bit-identical to
+ * the entries above (given a gradient that is zero at the masked pillars); the maximum, its arg-max and every gradient row exist per
+ * stage-1 TOKEN.  From the plan ("vfe.*" arena buffers): vis_rows (Nv) = pillar-major rows of the visible pillars, ascending; vis_tok (Nv) =
+ * token of each of those rows; row_tok (N) = token of each row's pillar or -1; tok_pillar (n_tok) ascending.  out / arg / g / gm are
+ * (n_tok, 128); arg holds pillar-major rows as above; M = number of ALL pillars (it fixes the partial sums' grouping). */
+int gdmae_vfe_max_layer_vis_fwd(const void* y1, long long N, const void* W, const int* vis_rows, const int* vis_tok, long long Nv,
+                                int n_tok, const float* gamma, const float* beta, double eps, double momentum,
+                                float* running_mean, float* running_var, long long* num_batches, double* stats, float* ab,
+                                float* mv, float* out, int* arg, void* workspace, void* stream);
+int gdmae_vfe_max_layer_vis_fwd_f16(const void* y1, long long N, const float* W, const int* vis_rows, const int* vis_tok, long long Nv,
+                                    int n_tok, const float* gamma, const float* beta, double eps, double momentum,
+                                    float* running_mean, float* running_var, long long* num_batches, double* stats, float* ab,
+                                    float* mv, float* out, int* arg, void* workspace, void* stream);
+int gdmae_vfe_max_layer_vis_bwd(const void* y1, long long N, const void* W, const int* row_tok, const int* tok_pillar, int n_tok, int M,
+                                const float* gamma, const double* stats, const float* ab, const float* out, const int* arg,
+                                const float* g, void* gm, void* dy1, float* dgamma, float* dbeta, float* dW, int accumulate,
+                                void* workspace, void* stream);
+int gdmae_vfe_max_layer_vis_bwd_f16(const void* y1, long long N, const float* W, const int* row_tok, const int* tok_pillar, int n_tok, int M,
+                                    const float* gamma, const double* stats, const float* ab, const float* out, const int* arg,
+                                    const float* g, void* gm, void* dy1, float* dgamma, float* dbeta, float* dW, int accumulate,
+                                    void* workspace, void* stream);
 int gdmae_segment_max(const float* x, const int* pillar_pt_off, const int* pillar_pts, int M, int C, float* out,
                       int* arg, void* stream);
 int gdmae_segment_max_bwd(const float* dout, const int* arg, const int* inverse32, long long N, int C, float* dx,
@@ -811,9 +833,11 @@ int gdmae_group_inner_inds(const long long* inverse_inds, long long n, long long
  * ("points", "point_coords", "inverse", "inverse32", "voxel_coords", "pillar_cell", "pt_off", "pillar_pts", "point_rank",
  * "sample_off", "pillar_mean", "cell2pillar"), "points_pm" / "row_pillar", "mask", "tok_pillar", per stage i "s<i>.tok_cell",
  * "s<i>.map", "s<i>.nbr_subm", "s<i>.nbr_subm_t", "s<i>.nbr_down", "s<i>.nbr_down_t", "s<i>.up_sites", per shift k
- * "s<i>.w<k>.{tok_win,tok_level,tok_slot,tok_pos,csr_tok,win_start,win_len}", "dec.tile_slot" / "dec.tile_list", and
+ * "s<i>.w<k>.{tok_win,tok_level,tok_slot,tok_pos,csr_tok,win_start,win_len}", "dec.tile_slot" / "dec.tile_list", when masked with
+ * pillar-major rows "vfe.row_tok" (N: token of each pillar-major row's pillar / -1), "vfe.vis_rows" / "vfe.vis_tok" (Nv: the rows of
+ * the visible pillars, ascending, and their tokens), "vfe.tok_row_off" (tokens + 1: first of each token's rows among those), and
  * "counts" = int32 [N points kept, M pillars | tokens of stage 0.. | 8 per (stage, shift): windows per level (3), tokens per
- * level (3), windows, tokens | active tiles | visible pillars] - the only thing the host has to read back.
+ * level (3), windows, tokens | active tiles | visible pillars | Nv rows of the visible pillars] - the only thing the host has to read back.
  * noise: (min(n_points, B*Y*X)) fp32 masking noise, one value per pillar in pillar order (null when !masked).
  * Outputs are bit-identical to the per-operator entry points above.
  * Limits (refused by the layout): B*Y*X < 2^31; per stage, the window grid B * (ceil(X/wx) + 1) * (ceil(Y/wy) + 1) AND the token
