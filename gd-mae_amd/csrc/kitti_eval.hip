@@ -16,10 +16,11 @@
 //   k_ke_match2      one wavefront per (chunk of kKeFrames frames, combo): compute_statistics_jit(compute_fp=True) for every frame of
 //                    the chunk and every threshold; lane t keeps the chunk's tp / fp / fn / similarity of threshold t.
 //   k_ke_reduce      one thread per (combo, threshold) adds the chunks in order.
-// No atomics anywhere: the result does not depend on scheduling.
-#include <limits.h>
-
+// No atomics anywhere: the result does not depend on scheduling.  The bodies of the two passes and of the reduce are those of
+// csrc/eval_match.h, shared with csrc/once_eval.hip; the rotated intersection is csrc/rect_clip.h.
 #include "common.h"
+#include "eval_match.h"
+#include "rect_clip.h"
 
 namespace {
 constexpr int kKeFrames = 8;          // frames per wavefront of the second pass (the unit of the fixed-order similarity sum)
@@ -37,65 +38,6 @@ struct KeArgs {
   const int *combo_cl, *combo_metric, *combo_ngt;
   const double* combo_min;
 };
-
-struct D2 {
-  double x, y;
-};
-
-// corners of the rectangle [x, z, l, w, ry] of a [x, y, z, l, h, w, ry] row relative to (ox, oy), in counter-clockwise order.
-// rotation_y turns clockwise in the (x, z) plane (the reference's rbbox_to_corners): the rotation is by -ry.  The sign matters: two
-// boxes displaced along their length under one convention are displaced across their width under the other.
-__device__ inline void ke_corners(const float* b, double ox, double oy, D2 (&c)[4]) {
-  const double cs = cos((double)b[6]), sn = -sin((double)b[6]);
-  const double hx = 0.5 * (double)b[3], hy = 0.5 * (double)b[5], cx = (double)b[0] - ox, cy = (double)b[2] - oy;
-  const double lx[4] = {-hx, hx, hx, -hx}, ly[4] = {-hy, -hy, hy, hy};
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    c[k].x = cx + lx[k] * cs - ly[k] * sn;
-    c[k].y = cy + lx[k] * sn + ly[k] * cs;
-  }
-}
-
-// area of the intersection of the two rectangles: the subject polygon clipped by the four edges of the other (no margin)
-__device__ inline double ke_rect_intersection(const float* a, const float* b) {
-  const double ra = 0.5 * sqrt((double)a[3] * a[3] + (double)a[5] * a[5]), rb = 0.5 * sqrt((double)b[3] * b[3] + (double)b[5] * b[5]);
-  const double dx = (double)a[0] - (double)b[0], dy = (double)a[2] - (double)b[2], reach = ra + rb + 1e-3;
-  if (dx * dx + dy * dy > reach * reach) return 0.0;       // the circumscribed circles do not meet: the intersection is empty
-  D2 clip[4], p[8], q[8];
-  ke_corners(b, (double)a[0], (double)a[2], clip);          // coordinates relative to a's centre
-  {
-    D2 ca[4];
-    ke_corners(a, (double)a[0], (double)a[2], ca);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) p[k] = ca[k];
-  }
-  int n = 4;
-  for (int e = 0; e < 4; ++e) {
-    const D2 p0 = clip[e], p1 = clip[(e + 1) & 3];
-    const double ex = p1.x - p0.x, ey = p1.y - p0.y;
-    int m = 0;
-    for (int k = 0; k < n; ++k) {
-      const D2 c = p[k], nx = p[k + 1 == n ? 0 : k + 1];
-      const double sc = ex * (c.y - p0.y) - ey * (c.x - p0.x), sn = ex * (nx.y - p0.y) - ey * (nx.x - p0.x);
-      if (sc >= 0.0 && m < 8) q[m++] = c;
-      if ((sc >= 0.0) != (sn >= 0.0) && m < 8) {
-        const double t = sc / (sc - sn);
-        q[m].x = c.x + t * (nx.x - c.x);
-        q[m].y = c.y + t * (nx.y - c.y);
-        ++m;
-      }
-    }
-    n = m;
-    if (n == 0) return 0.0;
-    for (int k = 0; k < n; ++k) p[k] = q[k];
-  }
-  double s = 0.0;
-  for (int k = 0; k < n; ++k) {
-    const D2 c = p[k], nx = p[k + 1 == n ? 0 : k + 1];
-    s += c.x * nx.y - nx.x * c.y;
-  }
-  return fabs(s) * 0.5;
-}
 
 // image overlap of boxes [x1, y1, x2, y2]: criterion -1 (IoU) or 0 (divided by the area of a)
 __device__ inline double ke_image_overlap(const float* a, const float* b, bool iou) {
@@ -118,7 +60,10 @@ __global__ __launch_bounds__(256) void k_ke_overlaps(KeArgs A, float* __restrict
     const float* gb = A.gt_geo + (size_t)(g0 + g) * 7;
     const float* db = A.dt_geo + (size_t)(d0 + j) * 7;
     overlaps[base + i] = (float)ke_image_overlap(A.dt_box + (size_t)(d0 + j) * 4, A.gt_box + (size_t)(g0 + g) * 4, true);
-    const double inter = ke_rect_intersection(db, gb);
+    // rotation_y turns CLOCKWISE in the (x, z) plane (the reference's rbbox_to_corners): the rotation is by -ry.  The sign matters: two
+    // boxes displaced along their length under one convention are displaced across their width under the other.
+    const double inter = rc_intersection((double)db[0], (double)db[2], (double)db[3], (double)db[5], -(double)db[6], (double)gb[0],
+                                         (double)gb[2], (double)gb[3], (double)gb[5], -(double)gb[6]);
     double bev = 0.0, d3 = 0.0;
     if (inter > 0.0) {
       bev = inter / ((double)db[3] * db[5] + (double)gb[3] * gb[5] - inter);
@@ -138,68 +83,18 @@ __global__ __launch_bounds__(256) void k_ke_overlaps(KeArgs A, float* __restrict
   }
 }
 
-// the wavefront's (largest v, lowest index among equal v); idx INT_MAX = none
-__device__ inline void ke_argmax(float& v, int& idx) {
-#pragma unroll
-  for (int d = GD_WAVE / 2; d > 0; d >>= 1) {
-    const float ov = __shfl_xor(v, d, GD_WAVE);
-    const int oi = __shfl_xor(idx, d, GD_WAVE);
-    if (oi != INT_MAX && (idx == INT_MAX || ov > v || (ov == v && oi < idx))) {
-      v = ov;
-      idx = oi;
-    }
-  }
-}
-__device__ inline int ke_wave_min(int v) {
-#pragma unroll
-  for (int d = GD_WAVE / 2; d > 0; d >>= 1) v = min(v, __shfl_xor(v, d, GD_WAVE));
-  return v;
-}
-__device__ inline int ke_wave_sum(int v) {
-#pragma unroll
-  for (int d = GD_WAVE / 2; d > 0; d >>= 1) v += __shfl_xor(v, d, GD_WAVE);
-  return v;
+// (frame f, combo k): the metric's overlap plane, the class's flag rows, the scores
+__device__ inline EmView ke_view(const KeArgs& A, const float* overlaps, int f, int k) {
+  const int g0 = A.gt_off[f], d0 = A.dt_off[f], cl = A.combo_cl[k];
+  return {overlaps + (size_t)A.combo_metric[k] * A.NP + A.pair_off[f], A.gt_off[f + 1] - g0, A.dt_off[f + 1] - d0,
+          A.ign_gt + (size_t)cl * A.NG + g0, A.ign_dt + (size_t)cl * A.ND + d0, A.dt_score + d0, A.combo_min[k]};
 }
 
 __global__ __launch_bounds__(256) void k_ke_match1(KeArgs A, const float* __restrict__ overlaps, float* __restrict__ matched) {
   const int f = blockIdx.x, lane = threadIdx.x & (GD_WAVE - 1), k = blockIdx.y * (256 / GD_WAVE) + threadIdx.x / GD_WAVE;
   if (k >= A.K) return;                                      // whole wavefronts leave together
-  const int g0 = A.gt_off[f], G = A.gt_off[f + 1] - g0, d0 = A.dt_off[f], D = A.dt_off[f + 1] - d0;
-  const int cl = A.combo_cl[k];
-  const double min_ov = A.combo_min[k];
-  const float* ov = overlaps + (size_t)A.combo_metric[k] * A.NP + A.pair_off[f];
-  const signed char* ig = A.ign_gt + (size_t)cl * A.NG + g0;
-  const signed char* id = A.ign_dt + (size_t)cl * A.ND + d0;
-  const float* sc = A.dt_score + d0;
-  const int nI = (D + GD_WAVE - 1) / GD_WAVE;
-  unsigned live = 0, assigned = 0;
-  for (int i = 0; i < nI; ++i) {
-    const int j = lane + GD_WAVE * i;
-    if (j < D && id[j] != -1) live |= 1u << i;
-  }
-  for (int g = 0; g < G; ++g) {
-    float out = -INFINITY;
-    const int ign_g = ig[g];
-    if (ign_g != -1) {
-      float bs = -10000000.f;                                // the reference's NO_DETECTION: a score at or below it never matches
-      int bj = INT_MAX;
-      const unsigned m = live & ~assigned;
-      for (int i = 0; i < nI; ++i)
-        if ((m >> i) & 1u) {
-          const int j = lane + GD_WAVE * i;
-          if ((double)ov[(size_t)g * D + j] > min_ov && sc[j] > bs) {
-            bs = sc[j];
-            bj = j;
-          }
-        }
-      ke_argmax(bs, bj);
-      if (bj != INT_MAX) {
-        if (lane == (bj & (GD_WAVE - 1))) assigned |= 1u << (bj / GD_WAVE);
-        if (!(ign_g == 1 || id[bj] == 1)) out = bs;
-      }
-    }
-    if (lane == 0) matched[(size_t)k * A.NG + g0 + g] = out;
-  }
+  // the sentinel is the reference's NO_DETECTION
+  em_first_pass(ke_view(A, overlaps, f, k), lane, -10000000.f, matched + (size_t)k * A.NG + A.gt_off[f]);
 }
 
 __global__ __launch_bounds__(GD_WAVE) void k_ke_thresholds(KeArgs A, const float* __restrict__ sorted, float* __restrict__ thresholds,
@@ -208,7 +103,7 @@ __global__ __launch_bounds__(GD_WAVE) void k_ke_thresholds(KeArgs A, const float
   const float* row = sorted + (size_t)k * A.NG;
   int n = 0;
   for (int i = lane; i < A.NG; i += GD_WAVE) n += row[i] > -INFINITY ? 1 : 0;
-  n = ke_wave_sum(n);
+  n = em_wave_sum(n);
   int nt = 0;
   if (lane == 0) {
     const double num_gt = (double)A.combo_ngt[k];
@@ -226,114 +121,48 @@ __global__ __launch_bounds__(GD_WAVE) void k_ke_thresholds(KeArgs A, const float
   if (lane >= nt && lane < kKePts) thresholds[k * kKePts + lane] = 0.f;
 }
 
+// the orientation similarity of the true positives of one wavefront: GT rows in order within a (frame, threshold), these sums in
+// frame order into the lane's threshold
+struct KeSimilarity {
+  bool on;                                                   // asked for, and the combo's metric is bbox
+  const float *gt_alpha, *dt_alpha;                          // of the frame at hand
+  double sim = 0.0, acc = 0.0;
+  __device__ void hit(int g, int j) {
+    if (on) sim += (1.0 + cos((double)gt_alpha[g] - (double)dt_alpha[j])) / 2.0;
+  }
+  __device__ void end(bool mine) {
+    if (mine) acc += sim;
+    sim = 0.0;
+  }
+};
+
 __global__ __launch_bounds__(256) void k_ke_match2(KeArgs A, const float* __restrict__ overlaps, const float* __restrict__ dc_max,
                                                    const float* __restrict__ thresholds, const int* __restrict__ n_thresholds,
                                                    int compute_aos, int* __restrict__ part_i, double* __restrict__ part_s) {
   const int chunk = blockIdx.x, lane = threadIdx.x & (GD_WAVE - 1), k = blockIdx.y * (256 / GD_WAVE) + threadIdx.x / GD_WAVE;
   if (k >= A.K) return;
-  const int cl = A.combo_cl[k], metric = A.combo_metric[k], nt = n_thresholds[k];
-  const double min_ov = A.combo_min[k];
-  int acc_tp = 0, acc_fp = 0, acc_fn = 0;
-  double acc_sim = 0.0;
+  const int metric = A.combo_metric[k], nt = n_thresholds[k];
+  EmCounts acc;
+  KeSimilarity sim{compute_aos && metric == 0, nullptr, nullptr};
   for (int f = chunk * kKeFrames; f < min((chunk + 1) * kKeFrames, A.F); ++f) {
-    const int g0 = A.gt_off[f], G = A.gt_off[f + 1] - g0, d0 = A.dt_off[f], D = A.dt_off[f + 1] - d0;
-    const float* ov = overlaps + (size_t)metric * A.NP + A.pair_off[f];
-    const signed char* ig = A.ign_gt + (size_t)cl * A.NG + g0;
-    const signed char* id = A.ign_dt + (size_t)cl * A.ND + d0;
-    const float* sc = A.dt_score + d0;
-    const int nI = (D + GD_WAVE - 1) / GD_WAVE;
-    unsigned live0 = 0, live1 = 0, stuff = 0;               // ignored_det 0 / 1; over a DontCare box (metric 0)
-    for (int i = 0; i < nI; ++i) {
+    const EmView v = ke_view(A, overlaps, f, k);
+    const int g0 = A.gt_off[f], d0 = A.dt_off[f];
+    unsigned stuff = 0;                                      // over a DontCare box (metric 0): never a false positive
+    for (int i = 0; metric == 0 && i * GD_WAVE < v.D; ++i) {
       const int j = lane + GD_WAVE * i;
-      if (j < D) {
-        if (id[j] == 0) live0 |= 1u << i;
-        if (id[j] == 1) live1 |= 1u << i;
-        if (metric == 0 && (double)dc_max[d0 + j] > min_ov) stuff |= 1u << i;
-      }
+      if (j < v.D && (double)dc_max[d0 + j] > v.min_ov) stuff |= 1u << i;
     }
-    for (int t = 0; t < nt; ++t) {
-      const float thr = thresholds[k * kKePts + t];
-      unsigned keep = 0, assigned = 0;
-      for (int i = 0; i < nI; ++i) {
-        const int j = lane + GD_WAVE * i;
-        if (j < D && !(sc[j] < thr)) keep |= 1u << i;
-      }
-      const unsigned c0 = live0 & keep, c1 = live1 & keep;
-      int tp = 0, fn = 0;
-      double sim = 0.0;
-      for (int g = 0; g < G; ++g) {
-        const int ign_g = ig[g];
-        if (ign_g == -1) continue;
-        // a non-ignored detection with the largest overlap (lowest index among equals) wins; without one, the first ignored detection
-        float bo = -1.f;
-        int bj = INT_MAX;
-        unsigned m = c0 & ~assigned;
-        for (int i = 0; i < nI; ++i)
-          if ((m >> i) & 1u) {
-            const int j = lane + GD_WAVE * i;
-            const float o = ov[(size_t)g * D + j];
-            if ((double)o > min_ov && o > bo) {
-              bo = o;
-              bj = j;
-            }
-          }
-        ke_argmax(bo, bj);
-        bool ignored_pick = false;
-        if (bj == INT_MAX) {
-          m = c1 & ~assigned;
-          for (int i = 0; i < nI && bj == INT_MAX; ++i)
-            if ((m >> i) & 1u) {
-              const int j = lane + GD_WAVE * i;
-              if ((double)ov[(size_t)g * D + j] > min_ov) bj = j;
-            }
-          bj = ke_wave_min(bj);
-          ignored_pick = true;
-        }
-        if (bj == INT_MAX) {
-          if (ign_g == 0) ++fn;
-        } else {
-          if (lane == (bj & (GD_WAVE - 1))) assigned |= 1u << (bj / GD_WAVE);
-          if (!(ign_g == 1 || ignored_pick)) {
-            ++tp;
-            if (compute_aos && metric == 0) sim += (1.0 + cos((double)A.gt_alpha[g0 + g] - (double)A.dt_alpha[d0 + bj])) / 2.0;
-          }
-        }
-      }
-      const int fp = ke_wave_sum(__popc(c0 & ~assigned & ~stuff));
-      if (lane == t) {
-        acc_tp += tp;
-        acc_fp += fp;
-        acc_fn += fn;
-        acc_sim += sim;
-      }
-    }
+    sim.gt_alpha = A.gt_alpha + g0, sim.dt_alpha = A.dt_alpha + d0;
+    em_second_pass<kKePts>(v, lane, k, thresholds, nt, stuff, sim, acc);
   }
-  if (lane < kKePts) {
-    const size_t o = ((size_t)chunk * A.K + k) * kKePts + lane;
-    part_i[o * 3 + 0] = acc_tp;
-    part_i[o * 3 + 1] = acc_fp;
-    part_i[o * 3 + 2] = acc_fn;
-    part_s[o] = acc_sim;
-  }
+  const size_t o = ((size_t)chunk * A.K + k) * kKePts + lane;
+  em_store_part<kKePts>(acc, lane, o, part_i);
+  if (lane < kKePts) part_s[o] = sim.acc;
 }
 
 __global__ __launch_bounds__(256) void k_ke_reduce(int n_chunks, int K, const int* __restrict__ part_i, const double* __restrict__ part_s,
                                                    long long* __restrict__ pr_counts, double* __restrict__ pr_sim) {
-  const int i = blockIdx.x * 256 + threadIdx.x;              // (combo, threshold)
-  if (i >= K * kKePts) return;
-  long long tp = 0, fp = 0, fn = 0;
-  double sim = 0.0;
-  for (int c = 0; c < n_chunks; ++c) {
-    const size_t o = (size_t)c * K * kKePts + i;
-    tp += part_i[o * 3 + 0];
-    fp += part_i[o * 3 + 1];
-    fn += part_i[o * 3 + 2];
-    sim += part_s[o];
-  }
-  pr_counts[i * 3 + 0] = tp;
-  pr_counts[i * 3 + 1] = fp;
-  pr_counts[i * 3 + 2] = fn;
-  pr_sim[i] = sim;
+  em_reduce<kKePts>(blockIdx.x * 256 + threadIdx.x, n_chunks, K, part_i, part_s, pr_counts, pr_sim);
 }
 
 size_t ke_part_i_bytes(int n_frames, int n_combos) { return gd_align((size_t)gd_div_up(n_frames, kKeFrames) * n_combos * kKePts * 3 * sizeof(int)); }

@@ -15,10 +15,10 @@
 //   k_oe_match2      one wavefront per (chunk of kOeFrames frames, combo): compute_statistics for every frame of the chunk and every
 //                    threshold; lane t keeps the chunk's tp / fp / fn of threshold t.
 //   k_oe_reduce      one thread per (combo, threshold) adds the chunks in order.
-// No atomics anywhere: the result does not depend on scheduling.
-#include <limits.h>
-
+// No atomics anywhere: the result does not depend on scheduling.  The bodies of the two passes and of the reduce are those of
+// csrc/eval_match.h, shared with csrc/kitti_eval.hip; the rotated intersection is csrc/rect_clip.h.
 #include "common.h"
+#include "eval_match.h"
 #include "rect_clip.h"
 
 namespace {
@@ -91,44 +91,17 @@ __global__ __launch_bounds__(256) void k_oe_overlaps(OeArgs A, float* __restrict
   for (int j = threadIdx.x; j < D; j += 256) oe_write_flags(A, A.pd_box + (size_t)(d0 + j) * 7, A.pd_code[d0 + j], flag_pd, A.ND, d0 + j);
 }
 
+// (frame f, combo k): the one overlap plane, the combo's flag rows, the scores
+__device__ inline EmView oe_view(const OeArgs& A, const float* overlaps, int f, int k) {
+  const int g0 = A.gt_off[f], d0 = A.pd_off[f];
+  return {overlaps + A.pair_off[f], A.gt_off[f + 1] - g0, A.pd_off[f + 1] - d0, A.flag_gt + (size_t)k * A.NG + g0,
+          A.flag_pd + (size_t)k * A.ND + d0, A.pd_score + d0, A.iou_thr[k / A.B]};
+}
+
 __global__ __launch_bounds__(256) void k_oe_match1(OeArgs A, const float* __restrict__ overlaps, float* __restrict__ matched) {
   const int f = blockIdx.x, lane = threadIdx.x & (GD_WAVE - 1), k = blockIdx.y * (256 / GD_WAVE) + threadIdx.x / GD_WAVE;
   if (k >= A.K) return;                                      // whole wavefronts leave together
-  const int g0 = A.gt_off[f], G = A.gt_off[f + 1] - g0, d0 = A.pd_off[f], D = A.pd_off[f + 1] - d0;
-  const double min_ov = A.iou_thr[k / A.B];
-  const float* ov = overlaps + A.pair_off[f];
-  const signed char* ig = A.flag_gt + (size_t)k * A.NG + g0;
-  const signed char* id = A.flag_pd + (size_t)k * A.ND + d0;
-  const float* sc = A.pd_score + d0;
-  const int nI = (D + GD_WAVE - 1) / GD_WAVE;
-  unsigned live = 0, assigned = 0;
-  for (int i = 0; i < nI; ++i) {
-    const int j = lane + GD_WAVE * i;
-    if (j < D && id[j] != -1) live |= 1u << i;
-  }
-  for (int g = 0; g < G; ++g) {
-    float out = -INFINITY;
-    const int ign_g = ig[g];
-    if (ign_g != -1) {
-      float bs = -1.f;                                       // the reference's sentinel: a score at or below it never matches
-      int bj = INT_MAX;
-      const unsigned m = live & ~assigned;
-      for (int i = 0; i < nI; ++i)
-        if ((m >> i) & 1u) {
-          const int j = lane + GD_WAVE * i;
-          if ((double)ov[(size_t)g * D + j] > min_ov && sc[j] > bs) {
-            bs = sc[j];
-            bj = j;
-          }
-        }
-      rc_wave_argmax(bs, bj);
-      if (bj != INT_MAX) {
-        if (lane == (bj & (GD_WAVE - 1))) assigned |= 1u << (bj / GD_WAVE);
-        if (!(ign_g == 1 || id[bj] == 1)) out = bs;
-      }
-    }
-    if (lane == 0) matched[(size_t)k * A.NG + g0 + g] = out;
-  }
+  em_first_pass(oe_view(A, overlaps, f, k), lane, -1.f, matched + (size_t)k * A.NG + A.gt_off[f]);      // -1: the reference's sentinel
 }
 
 __global__ __launch_bounds__(GD_WAVE) void k_oe_thresholds(OeArgs A, const float* __restrict__ sorted, int* __restrict__ num_valid,
@@ -141,8 +114,8 @@ __global__ __launch_bounds__(GD_WAVE) void k_oe_thresholds(OeArgs A, const float
     n += row[i] > -INFINITY ? 1 : 0;
     nv += ig[i] == 0 ? 1 : 0;
   }
-  n = rc_wave_sum(n);
-  nv = rc_wave_sum(nv);
+  n = em_wave_sum(n);
+  nv = em_wave_sum(nv);
   if (nv == 0) n = 0;                                        // no true positive without a valid GT row
   int nt = 0;
   if (lane == 0) {
@@ -174,94 +147,15 @@ __global__ __launch_bounds__(256) void k_oe_match2(OeArgs A, const float* __rest
   const int chunk = blockIdx.x, lane = threadIdx.x & (GD_WAVE - 1), k = blockIdx.y * (256 / GD_WAVE) + threadIdx.x / GD_WAVE;
   if (k >= A.K) return;
   const int nt = min(n_thresholds[k], kOePts);
-  const double min_ov = A.iou_thr[k / A.B];
-  int acc_tp = 0, acc_fp = 0, acc_fn = 0;
-  for (int f = chunk * kOeFrames; f < min((chunk + 1) * kOeFrames, A.F); ++f) {
-    const int g0 = A.gt_off[f], G = A.gt_off[f + 1] - g0, d0 = A.pd_off[f], D = A.pd_off[f + 1] - d0;
-    const float* ov = overlaps + A.pair_off[f];
-    const signed char* ig = A.flag_gt + (size_t)k * A.NG + g0;
-    const signed char* id = A.flag_pd + (size_t)k * A.ND + d0;
-    const float* sc = A.pd_score + d0;
-    const int nI = (D + GD_WAVE - 1) / GD_WAVE;
-    unsigned live0 = 0, live1 = 0;                           // predictions flagged 0 / 1
-    for (int i = 0; i < nI; ++i) {
-      const int j = lane + GD_WAVE * i;
-      if (j < D) {
-        if (id[j] == 0) live0 |= 1u << i;
-        if (id[j] == 1) live1 |= 1u << i;
-      }
-    }
-    for (int t = 0; t < nt; ++t) {
-      const float thr = thresholds[k * kOePts + t];
-      unsigned keep = 0, assigned = 0;
-      for (int i = 0; i < nI; ++i) {
-        const int j = lane + GD_WAVE * i;
-        if (j < D && !(sc[j] < thr)) keep |= 1u << i;
-      }
-      const unsigned c0 = live0 & keep, c1 = live1 & keep;
-      int tp = 0, fn = 0;
-      for (int g = 0; g < G; ++g) {
-        const int ign_g = ig[g];
-        if (ign_g == -1) continue;
-        // a flag-0 prediction with the largest overlap (lowest index among equals) wins; without one, the first flag-1 prediction
-        float bo = -1.f;
-        int bj = INT_MAX;
-        unsigned m = c0 & ~assigned;
-        for (int i = 0; i < nI; ++i)
-          if ((m >> i) & 1u) {
-            const int j = lane + GD_WAVE * i;
-            const float o = ov[(size_t)g * D + j];
-            if ((double)o > min_ov && o > bo) {
-              bo = o;
-              bj = j;
-            }
-          }
-        rc_wave_argmax(bo, bj);
-        bool ignored_pick = false;
-        if (bj == INT_MAX) {
-          m = c1 & ~assigned;
-          for (int i = 0; i < nI && bj == INT_MAX; ++i)
-            if ((m >> i) & 1u) {
-              const int j = lane + GD_WAVE * i;
-              if ((double)ov[(size_t)g * D + j] > min_ov) bj = j;
-            }
-          bj = rc_wave_min(bj);
-          ignored_pick = true;
-        }
-        if (bj == INT_MAX) {
-          if (ign_g == 0) ++fn;
-        } else {
-          if (lane == (bj & (GD_WAVE - 1))) assigned |= 1u << (bj / GD_WAVE);
-          if (!(ign_g == 1 || ignored_pick)) ++tp;
-        }
-      }
-      const int fp = rc_wave_sum(__popc(c0 & ~assigned));
-      if (lane == t) {
-        acc_tp += tp;
-        acc_fp += fp;
-        acc_fn += fn;
-      }
-    }
-  }
-  const size_t o = ((size_t)chunk * A.K + k) * kOePts + lane;
-  part[o * 3 + 0] = acc_tp;
-  part[o * 3 + 1] = acc_fp;
-  part[o * 3 + 2] = acc_fn;
+  EmCounts acc;
+  EmNoHook none;
+  for (int f = chunk * kOeFrames; f < min((chunk + 1) * kOeFrames, A.F); ++f)
+    em_second_pass<kOePts>(oe_view(A, overlaps, f, k), lane, k, thresholds, nt, 0u, none, acc);
+  em_store_part<kOePts>(acc, lane, ((size_t)chunk * A.K + k) * kOePts + lane, part);
 }
 
 __global__ __launch_bounds__(256) void k_oe_reduce(int n_chunks, int K, const int* __restrict__ part, long long* __restrict__ counts) {
-  const int i = blockIdx.x * 256 + threadIdx.x;              // (combo, threshold)
-  if (i >= K * kOePts) return;
-  long long tp = 0, fp = 0, fn = 0;
-  for (int c = 0; c < n_chunks; ++c) {
-    const size_t o = (size_t)c * K * kOePts + i;
-    tp += part[o * 3 + 0];
-    fp += part[o * 3 + 1];
-    fn += part[o * 3 + 2];
-  }
-  counts[i * 3 + 0] = tp;
-  counts[i * 3 + 1] = fp;
-  counts[i * 3 + 2] = fn;
+  em_reduce<kOePts>(blockIdx.x * 256 + threadIdx.x, n_chunks, K, part, nullptr, counts, nullptr);
 }
 
 int oe_host_bands(int mode) { return mode == 0 ? 1 : mode == 1 ? 3 : 4; }

@@ -1,10 +1,8 @@
-// Exact intersection area of two rotated rectangles on plain doubles (cx, cy, dx, dy, angle), and the wave64 reductions of the
-// evaluator kernels (csrc/once_eval.hip).  The clipping is the one of csrc/kitti_eval.hip: the subject polygon
-// cut by the four edges of the other rectangle in fp64, no vertex sort, no corner margin.  Folding the two files onto this header
-// is a follow-up: kitti_eval.hip keeps its own copy so that its compiled code does not move.
+// Exact intersection area of two rotated rectangles on plain doubles (cx, cy, dx, dy, angle): the one clipping of the AP evaluators
+// (csrc/kitti_eval.hip on the (x, z) plane; csrc/once_eval.hip on (x, y)).  The subject polygon is cut by the
+// four edges of the other rectangle in fp64: no vertex sort and no corner margin (bev_iou.h, the NMS contract, keeps its 1e-2 m
+// margin and is a different thing).  Geometry only: the matching of the evaluators is csrc/eval_match.h.
 #pragma once
-#include <limits.h>
-
 #include "common.h"
 
 struct RcPoint {
@@ -65,27 +63,4 @@ __device__ inline double rc_intersection(double ax, double ay, double adx, doubl
     s += c.x * nx.y - nx.x * c.y;
   }
   return fabs(s) * 0.5;
-}
-
-// the wavefront's (largest v, lowest index among equal v); idx INT_MAX = none
-__device__ inline void rc_wave_argmax(float& v, int& idx) {
-#pragma unroll
-  for (int d = GD_WAVE / 2; d > 0; d >>= 1) {
-    const float ov = __shfl_xor(v, d, GD_WAVE);
-    const int oi = __shfl_xor(idx, d, GD_WAVE);
-    if (oi != INT_MAX && (idx == INT_MAX || ov > v || (ov == v && oi < idx))) {
-      v = ov;
-      idx = oi;
-    }
-  }
-}
-__device__ inline int rc_wave_min(int v) {
-#pragma unroll
-  for (int d = GD_WAVE / 2; d > 0; d >>= 1) v = min(v, __shfl_xor(v, d, GD_WAVE));
-  return v;
-}
-__device__ inline int rc_wave_sum(int v) {
-#pragma unroll
-  for (int d = GD_WAVE / 2; d > 0; d >>= 1) v += __shfl_xor(v, d, GD_WAVE);
-  return v;
 }

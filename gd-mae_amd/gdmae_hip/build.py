@@ -52,8 +52,8 @@ def build(force: bool = False, verbose: bool = True) -> str:
             own = own + [os.path.join(CSRC, "bev_iou.h")]
         if s in ("roi_targets.hip", "recall_record.hip"):
             own = own + [os.path.join(CSRC, "iou3d_rows.h")]
-        if s == "once_eval.hip":
-            own = [os.path.join(CSRC, "rect_clip.h")]
+        if s in ("kitti_eval.hip", "once_eval.hip"):
+            own = [os.path.join(CSRC, "rect_clip.h"), os.path.join(CSRC, "eval_match.h")]
         if s in ("input_pipeline.hip", "gt_sampling.hip"):
             own = own + [os.path.join(CSRC, "aug_xform.h")]
         if force or _newer(src, obj) or any(_newer(d, obj) for d in deps + own):

@@ -408,56 +408,69 @@ def kitti_statement_overlaps(gt, dt, dc_box, bev_overlap):
     return ov, image(a, dc_box.astype(np.float64)[None, :, :], False)
 
 
-def _statement_first_pass(ov, score, ign_gt, ign_dt, min_ov):
-    """``compute_statistics_jit(compute_fp=False)`` on one frame: ov (D, G) -> the true positives' scores per GT row, -inf elsewhere."""
-    D, G = ov.shape
-    out, assigned = np.full(G, -np.inf, np.float32), np.zeros(D, bool)
-    live = (ign_dt != -1) & (score > KITTI_NO_DETECTION)
+def _first_pass(enough, score, flag_gt, flag_pred, sentinel):
+    """The first greedy pass of both evaluators on one frame (KITTI ``compute_statistics_jit(compute_fp=False)``, ONCE
+    ``accumulate_scores``): enough (G, P) bool, "this pair overlaps enough" -> the true positives' scores per GT row, -inf elsewhere.
+    A flag is -1 (not of this combo), 0 (counts) or 1 (ignored); a score at or below ``sentinel`` never matches."""
+    G, P = enough.shape
+    out, assigned = np.full(G, -np.inf, np.float32), np.zeros(P, bool)
+    live = (flag_pred != -1) & (score > sentinel)
     for g in range(G):
-        if ign_gt[g] == -1:
+        if flag_gt[g] == -1:
             continue
-        cand = live & ~assigned & (ov[:, g] > min_ov)
+        cand = live & ~assigned & enough[g]
         if not cand.any():
             continue
         j = int(np.argmax(np.where(cand, score, -np.inf)))      # the highest score; among equal scores the lowest index (strict >)
         assigned[j] = True
-        if not (ign_gt[g] == 1 or ign_dt[j] == 1):
+        if not (flag_gt[g] == 1 or flag_pred[j] == 1):
             out[g] = score[j]
     return out
 
 
-def _statement_second_pass(ov, score, gt_alpha, dt_alpha, ign_gt, ign_dt, dc_max, min_ov, thresholds, compute_aos):
-    """``compute_statistics_jit(compute_fp=True)`` on one frame for all T thresholds at once -> tp, fp, fn (T) int64, sim (T) fp64.
-    Per GT row the reference's loop over the detections ends with the non-ignored candidate of the largest overlap (the first of
-    equals), and only without one with the FIRST candidate among the ``ignored 1`` detections."""
-    D, G = ov.shape
+def _second_pass(ov, enough, score, flag_gt, flag_pred, thresholds):
+    """The second greedy pass of both evaluators on one frame (KITTI ``compute_statistics_jit(compute_fp=True)``, ONCE
+    ``compute_statistics``) for all T thresholds at once: ov / enough (G, P) -> tp, fn (T) int64, keep, assigned (T, P) bool (at or
+    above the threshold; taken by a GT row), picked (G, T) int64 (the prediction of a true positive, -1 elsewhere).  Per GT row the
+    reference's loop over the predictions ends with the flag-0 candidate of the largest overlap (the first of equals), and only
+    without one with the FIRST flag-1 candidate.  False positives are the caller's: the two evaluators count them differently."""
+    G, P = ov.shape
     T = len(thresholds)
     keep = ~(score[None, :] < np.asarray(thresholds, np.float32)[:, None])
-    c0, c1 = keep & (ign_dt == 0)[None, :], keep & (ign_dt == 1)[None, :]
-    assigned = np.zeros((T, D), bool)
-    tp, fn, sim, rows = np.zeros(T, np.int64), np.zeros(T, np.int64), np.zeros(T, np.float64), np.arange(T)
+    c0, c1 = keep & (flag_pred == 0)[None, :], keep & (flag_pred == 1)[None, :]
+    assigned, picked = np.zeros((T, P), bool), np.full((G, T), -1, np.int64)
+    tp, fn, rows = np.zeros(T, np.int64), np.zeros(T, np.int64), np.arange(T)
     for g in range(G):
-        if ign_gt[g] == -1 or D == 0:
-            fn += int(ign_gt[g] == 0)
+        if flag_gt[g] == -1 or P == 0:
+            fn += int(flag_gt[g] == 0)
             continue
-        over = (ov[:, g] > min_ov)[None, :]
-        m0 = c0 & ~assigned & over
+        m0 = c0 & ~assigned & enough[g][None, :]
         has0 = m0.any(axis=1)
-        j0 = np.argmax(np.where(m0, ov[:, g][None, :], -1.0), axis=1)
-        m1 = c1 & ~assigned & over
+        j0 = np.argmax(np.where(m0, ov[g][None, :], -1.0), axis=1)
+        m1 = c1 & ~assigned & enough[g][None, :]
         has1 = m1.any(axis=1) & ~has0
         j = np.where(has0, j0, np.argmax(m1, axis=1))
         found = has0 | has1
-        if ign_gt[g] == 0:
+        if flag_gt[g] == 0:
             fn += ~found
         assigned[rows[found], j[found]] = True
-        is_tp = has0 & (ign_gt[g] == 0)
+        is_tp = has0 & (flag_gt[g] == 0)
         tp += is_tp
-        if compute_aos:
-            sim += np.where(is_tp, (1.0 + np.cos(float(gt_alpha[g]) - dt_alpha[j].astype(np.float64))) / 2.0, 0.0)
-    left = c0 & ~assigned
+        picked[g, is_tp] = j[is_tp]
+    return tp, fn, keep, assigned, picked
+
+
+def _kitti_second_pass(ov, score, gt_alpha, dt_alpha, ign_gt, ign_dt, dc_max, min_ov, thresholds, compute_aos):
+    """``_second_pass`` on one frame's (D, G) overlaps -> tp, fp, fn (T) int64, sim (T) fp64.  A detection left over is no false
+    positive where it lies on a DontCare box (``dc_max``, metric 0); the similarity is summed over the GT rows in their order."""
+    tp, fn, keep, assigned, picked = _second_pass(ov.T, ov.T > min_ov, score, ign_gt, ign_dt, thresholds)
+    left = keep & (ign_dt == 0)[None, :] & ~assigned
     if dc_max is not None:
         left &= ~(dc_max > min_ov)[None, :]
+    sim = np.zeros(len(thresholds), np.float64)
+    for g in range(picked.shape[0] if compute_aos else 0):   # a Python loop: np.sum's pairwise order changes the last bits
+        hit = picked[g] >= 0
+        sim[hit] += (1.0 + np.cos(float(gt_alpha[g]) - dt_alpha[picked[g][hit]].astype(np.float64))) / 2.0
     return tp, left.sum(axis=1).astype(np.int64), fn, sim
 
 
@@ -492,14 +505,14 @@ def kitti_eval_numpy(gt_annos, dt_annos, class_names, PR_detail_dict=None, bev_o
     for k in range(K):
         cl, m, mn = combo_cl[k], combo_metric[k], combo_min[k]
         for f in range(F):
-            matched[k, go[f]:go[f + 1]] = _statement_first_pass(overlaps[f][m], score[do[f]:do[f + 1]], ig[cl, go[f]:go[f + 1]],
-                                                                idt[cl, do[f]:do[f + 1]], mn)
+            matched[k, go[f]:go[f + 1]] = _first_pass(overlaps[f][m].T > mn, score[do[f]:do[f + 1]], ig[cl, go[f]:go[f + 1]],
+                                                      idt[cl, do[f]:do[f + 1]], KITTI_NO_DETECTION)
         tps = np.sort(matched[k][matched[k] > -np.inf])[::-1]
         th = kitti_get_thresholds(tps, int(combo_ngt[k]))
         n_thr[k] = len(th)
         thresholds[k, :len(th)] = th
         for f in range(F):
-            tp, fp, fn, sim = _statement_second_pass(
+            tp, fp, fn, sim = _kitti_second_pass(
                 overlaps[f][m], score[do[f]:do[f + 1]], gt['alpha'][go[f]:go[f + 1]], dt['alpha'][do[f]:do[f + 1]], ig[cl, go[f]:go[f + 1]],
                 idt[cl, do[f]:do[f + 1]], dc_maxes[f] if m == 0 else None, mn, th, compute_aos and m == 0)
             n = len(th)
@@ -515,7 +528,34 @@ def kitti_eval_numpy(gt_annos, dt_annos, class_names, PR_detail_dict=None, bev_o
                              pr_sim=pr_sim, precision=precision, recall=recall, aos=aos, compute_aos=compute_aos, clean=cd)
 
 
-class KittiEval:
+class _StagedEval:
+    """The device run that ``KittiEval`` and ``OnceEval`` share: per-frame limits and pair offsets, uploads and allocations on
+    ``self.device``, and the two calls of the entry point (``self._call``, the subclass's argument list) with the descending sort of
+    the first pass's scores between them."""
+
+    def _frames(self, who, max_rows, gt_off, pred_off, pred_rows):
+        for what, off in (("GT rows", gt_off), (pred_rows, pred_off)):
+            if self.F and int(np.diff(off).max()) > max_rows:
+                raise ValueError(f"{who}: a frame with {int(np.diff(off).max())} {what} (at most {max_rows})")
+        self.pair_off = _offsets(np.diff(gt_off) * np.diff(pred_off))
+        self.NG, self.ND, self.NP = int(gt_off[-1]), int(pred_off[-1]), int(self.pair_off[-1])
+
+    def _up(self, a, t):
+        return torch.from_numpy(np.ascontiguousarray(a, t)).to(self.device)
+
+    def _empty(self, *shape, dtype=torch.float32):
+        return torch.empty(*shape, dtype=dtype, device=self.device)
+
+    def _run(self, L, workspace_bytes):
+        with torch.cuda.device(self.device):
+            ws_bytes = workspace_bytes(self.F, self.K)
+            ws = self._empty(max(ws_bytes, 1), dtype=torch.uint8)
+            self._call(L, 1, None, None, 0)
+            self._sorted = torch.sort(self._matched, dim=1, descending=True).values.contiguous()
+            self._call(L, 2, self._sorted, ws, ws_bytes)
+
+
+class KittiEval(_StagedEval):
     """The stages of ``kitti_eval`` as device tensors (csrc/kitti_eval.hip: five launches and one ``torch.sort`` between the two
     calls; no host read until ``curves``).  Geometry, boxes, alpha and SCORES are uploaded as fp32: scores are compared as fp32 values
     (two scores that differ only beyond fp32 are a tie, and the lowest detection index wins it, as the reference's strict ``>`` does
@@ -542,19 +582,14 @@ class KittiEval:
         else:
             self.compute_aos = kitti_compute_aos(dt_annos)
             cd = self.clean = kitti_clean_data(gt_annos, dt_annos, self.classes)
-        self.F, self.C = len(gt_annos), len(self.classes)
+        self.F, self.C, self.device = len(gt_annos), len(self.classes), device
         go, do = cd['gt_off'], cd['dt_off']
-        for what, off in (("GT rows", go), ("detections", do)):
-            if self.F and int(np.diff(off).max()) > KITTI_MAX_ROWS:
-                raise ValueError(f"kitti_eval: a frame with {int(np.diff(off).max())} {what} (at most {KITTI_MAX_ROWS})")
-        self.pair_off = _offsets(np.diff(go) * np.diff(do))
-        self.NG, self.ND, self.NP = int(go[-1]), int(do[-1]), int(self.pair_off[-1])
+        self._frames("kitti_eval", KITTI_MAX_ROWS, go, do, "detections")
         gt = kitti_geometry(gt_annos, False)
         cl, me, mn, ng = kitti_combos(self.classes, cd['num_valid'])
         self.K = len(cl)
         self._host = [np.ascontiguousarray(o, np.int32) for o in (go, do, cd['dc_off'])]          # kept alive: read by the entry point
-        up = lambda a, t: torch.from_numpy(np.ascontiguousarray(a, t)).to(device)      # noqa: E731
-        f32 = np.float32
+        up, e, f32 = self._up, self._empty, np.float32
         if record is not None:
             dt_side = [done['bbox'], done['geo'], done['alpha'], done['score']]
             ignored_dt = done['ignored_dt']
@@ -566,17 +601,11 @@ class KittiEval:
             up(gt['bbox'], f32), up(gt['geo'], f32), up(gt['alpha'], f32)] + dt_side + [
             up(gt['bbox'][cd['dc_rows']], f32), up(cd['ignored_gt'], np.int8), ignored_dt,
             up(cl, np.int32), up(me, np.int32), up(mn, np.float64), up(ng, np.int32)]
-        e = lambda *s, dtype=torch.float32: torch.empty(*s, dtype=dtype, device=device)      # noqa: E731
         self._overlaps, self._dc_max, self._matched = e(3, self.NP), e(self.ND), e(self.K, self.NG)
         self._thresholds, self._n_thr = e(self.K, KITTI_SAMPLE_PTS), e(self.K, dtype=torch.int32)
         self._pr_counts, self._pr_sim = e(self.K, KITTI_SAMPLE_PTS, 3, dtype=torch.int64), e(self.K, KITTI_SAMPLE_PTS, dtype=torch.float64)
         self._curves = None
-        with torch.cuda.device(device):
-            ws_bytes = L.load().gdmae_kitti_eval_workspace_bytes(self.F, self.K)
-            ws = e(max(ws_bytes, 1), dtype=torch.uint8)
-            self._call(L, 1, None, None, 0)
-            self._sorted = torch.sort(self._matched, dim=1, descending=True).values.contiguous()
-            self._call(L, 2, self._sorted, ws, ws_bytes)
+        self._run(L, L.load().gdmae_kitti_eval_workspace_bytes)
 
     def _call(self, L, stage, sorted_scores, ws, ws_bytes):
         hp = lambda a: a.ctypes.data      # noqa: E731
@@ -762,30 +791,24 @@ def kitti_annos_launch(boxes, scores, labels, num, calib, dt_off, n_det, class_m
     return out
 
 
-class KittiDetections:
-    """The detections of an evaluation loop as a padded device store (``rows`` rows per frame, grown by doubling) and, after
-    ``finish``, as the compact device tensors ``KittiEval`` reads.  ``update`` makes no host read and no launch of this library;
-    ``finish`` makes the one host read (the per-frame counts) and the one ``gdmae_kitti_annos`` launch."""
+class _DetectionStore:
+    """What ``KittiDetections`` and ``OnceDetections`` share: the padded device store (``rows`` rows per frame, the frames grown by
+    doubling) of boxes (cap, rows, 7) fp32, scores (cap, rows) fp32, labels (cap, rows) int64, num (cap) int32 and the subclass's
+    ``EXTRA`` per-frame fp32 tensors (name -> width).  A subclass names its row limit, the two hints of its CPU refusals, its
+    allocator and ``_invalidate`` (what it caches of the store's content)."""
+    MAX_ROWS, CPU_DEVICE, CPU_TENSORS, EXTRA = None, "", "", {}
+    ALLOC = staticmethod(torch.empty)
 
-    def __init__(self, class_names, device, rows=500, frames=0):
+    def __init__(self, class_names, device, rows):
+        self._who = type(self).__name__
         self.class_names = [str(c) for c in class_names]
         self.device = torch.device(device)
         if self.device.type != "cuda":
-            raise NotImplementedError("KittiDetections: CPU device (the annos are computed in libgdmae_hip.so, no CPU fallback; "
-                                      "kitti_annos_numpy is the CPU path)")
-        if not 1 <= rows <= KITTI_MAX_ROWS:
-            raise ValueError(f"KittiDetections: rows {rows} (1 .. {KITTI_MAX_ROWS})")
-        if not 1 <= len(self.class_names) <= KITTI_MAX_NAMES:
-            raise ValueError(f"KittiDetections: {len(self.class_names)} class names (1 .. {KITTI_MAX_NAMES})")
+            raise NotImplementedError(f"{self._who}: CPU device ({self.CPU_DEVICE})")
+        if not 1 <= rows <= self.MAX_ROWS:
+            raise ValueError(f"{self._who}: rows {rows} (1 .. {self.MAX_ROWS})")
         self.rows, self.F, self.frame_ids = int(rows), 0, []
-        self.class_map = kitti_class_map(self.class_names)
-        self._cap, self._store, self._pinned = 0, None, []
-        self._host_num = []                      # per update: the counts when the caller knows them on the host, else None
-        self._reserve(int(frames))
-        self._invalidate()
-
-    def _invalidate(self):
-        self._counts, self._first, self._done, self._annos, self._aos = None, None, {}, None, None
+        self._cap, self._store = 0, None
 
     def _reserve(self, need):
         if need <= self._cap:
@@ -793,9 +816,9 @@ class KittiDetections:
         cap = self._cap
         while cap < need:
             cap = max(2 * cap, 1)
-        e = lambda *s, dtype=torch.float32: torch.empty(*s, dtype=dtype, device=self.device)      # noqa: E731
+        e = lambda *s, dtype=torch.float32: self.ALLOC(*s, dtype=dtype, device=self.device)      # noqa: E731
         new = dict(boxes=e(cap, self.rows, 7), scores=e(cap, self.rows), labels=e(cap, self.rows, dtype=torch.int64),
-                   num=e(cap, dtype=torch.int32), calib=e(cap, KITTI_CALIB_FLOATS))
+                   num=e(cap, dtype=torch.int32), **{k: e(cap, width) for k, width in self.EXTRA.items()})
         if self._store is not None and self.F:
             for k, t in new.items():
                 t[:self.F].copy_(self._store[k][:self.F])
@@ -803,35 +826,33 @@ class KittiDetections:
 
     def widen(self, rows):
         """Reallocates the store with ``rows`` (> the present) rows per frame and copies what it holds: device copies, no host read."""
-        if not self.rows < rows <= KITTI_MAX_ROWS:
-            raise ValueError(f"KittiDetections.widen: rows {rows} ({self.rows + 1} .. {KITTI_MAX_ROWS})")
+        if not self.rows < rows <= self.MAX_ROWS:
+            raise ValueError(f"{self._who}.widen: rows {rows} ({self.rows + 1} .. {self.MAX_ROWS})")
         old, old_rows = self._store, self.rows
         self.rows, self._cap, self._store = int(rows), 0, None
         self._reserve(max(self.F, 1 if old is None else old['num'].shape[0]))
         if old is not None and self.F:
             for k in ('boxes', 'scores', 'labels'):
                 self._store[k][:self.F, :old_rows].copy_(old[k][:self.F])
-            for k in ('num', 'calib'):
+            for k in ('num', *self.EXTRA):
                 self._store[k][:self.F].copy_(old[k][:self.F])
         self._invalidate()
 
-    def update(self, out, batch_dict, host_num=None):
-        """out: the padded dict of ``detect`` (pred_boxes (B, n, >= 7), pred_scores (B, n), pred_labels (B, n), num (B)); batch_dict:
-        ``calib`` (B calibrations), ``image_shape`` (B, 2) = (height, width), ``frame_id`` (B).  No host read."""
+    def _checked(self, out):
+        """the padded dict of ``detect`` -> (boxes, scores, labels, num) after the shape and device checks of ``update``"""
         boxes, scores, labels, num = out['pred_boxes'], out['pred_scores'], out['pred_labels'], out['num']
         if boxes.dim() != 3 or boxes.shape[2] < 7 or tuple(scores.shape) != tuple(boxes.shape[:2]) or tuple(labels.shape) != tuple(
                 boxes.shape[:2]) or tuple(num.shape) != (boxes.shape[0],):
-            raise ValueError("KittiDetections.update: pred_boxes (B, n, >= 7), pred_scores / pred_labels (B, n), num (B)")
-        B, n = scores.shape
-        if n > self.rows:
-            raise ValueError(f"KittiDetections.update: n {n} rows per sample in a store of rows {self.rows}")
+            raise ValueError(f"{self._who}.update: pred_boxes (B, n, >= 7), pred_scores / pred_labels (B, n), num (B)")
+        if scores.shape[1] > self.rows:
+            raise ValueError(f"{self._who}.update: n {scores.shape[1]} rows per sample in a store of rows {self.rows}")
         if not all(t.is_cuda for t in (boxes, scores, labels, num)):
-            raise NotImplementedError("KittiDetections.update: CPU tensors (no CPU fallback; kitti_annos_numpy is the CPU path)")
-        calibs, shapes, ids = batch_dict['calib'], batch_dict['image_shape'], batch_dict['frame_id']
-        if len(calibs) != B or len(shapes) != B or len(ids) != B:
-            raise ValueError(f"KittiDetections.update: {B} samples, {len(calibs)} calibrations, {len(shapes)} image shapes, {len(ids)} frame ids")
-        on_device = isinstance(shapes, torch.Tensor) and shapes.is_cuda          # an image_shape already uploaded is not read back
-        packed = np.stack([kitti_pack_calib(calibs[b], None if on_device else _host(shapes[b], np.int64)) for b in range(B)])
+            raise NotImplementedError(f"{self._who}.update: CPU tensors ({self.CPU_TENSORS})")
+        return boxes, scores, labels, num
+
+    def _append(self, boxes, scores, labels, num, ids):
+        """copies the checked batch behind the frames held -> the slice of its frames in the store"""
+        B, n = scores.shape
         self._reserve(self.F + B)
         s, at = self._store, slice(self.F, self.F + B)
         if n:
@@ -839,15 +860,56 @@ class KittiDetections:
             s['scores'][at, :n].copy_(scores)
             s['labels'][at, :n].copy_(labels)
         s['num'][at].copy_(num)
-        pinned = torch.from_numpy(packed).pin_memory()                           # one small H2D copy that does not wait for the device
-        s['calib'][at].copy_(pinned, non_blocking=True)
-        self._pinned.append(pinned)                                              # alive until the copy has run (``counts`` waits)
-        if on_device:
-            s['calib'][at, 33:35].copy_(shapes[:, :2])
         self.frame_ids += list(ids)
-        self._host_num.append(None if host_num is None else [int(v) for v in host_num])
         self.F += B
         self._invalidate()
+        return at
+
+    def _counts_in_range(self, counts):
+        if counts.size and (counts.min() < 0 or counts.max() > self.rows):
+            raise ValueError(f"{self._who}: a frame count outside 0 .. {self.rows}")
+
+
+class KittiDetections(_DetectionStore):
+    """The detections of an evaluation loop as a padded device store (``rows`` rows per frame, grown by doubling) and, after
+    ``finish``, as the compact device tensors ``KittiEval`` reads.  ``update`` makes no host read and no launch of this library;
+    ``finish`` makes the one host read (the per-frame counts) and the one ``gdmae_kitti_annos`` launch."""
+
+    MAX_ROWS, EXTRA = KITTI_MAX_ROWS, {'calib': KITTI_CALIB_FLOATS}
+    CPU_DEVICE = "the annos are computed in libgdmae_hip.so, no CPU fallback; kitti_annos_numpy is the CPU path"
+    CPU_TENSORS = "no CPU fallback; kitti_annos_numpy is the CPU path"
+
+    def __init__(self, class_names, device, rows=500, frames=0):
+        super().__init__(class_names, device, rows)
+        if not 1 <= len(self.class_names) <= KITTI_MAX_NAMES:
+            raise ValueError(f"KittiDetections: {len(self.class_names)} class names (1 .. {KITTI_MAX_NAMES})")
+        self.class_map = kitti_class_map(self.class_names)
+        self._pinned = []
+        self._host_num = []                      # per update: the counts when the caller knows them on the host, else None
+        self._reserve(int(frames))
+        self._invalidate()
+
+    def _invalidate(self):
+        self._counts, self._first, self._done, self._annos, self._aos = None, None, {}, None, None
+
+    def update(self, out, batch_dict, host_num=None):
+        """out: the padded dict of ``detect`` (pred_boxes (B, n, >= 7), pred_scores (B, n), pred_labels (B, n), num (B)); batch_dict:
+        ``calib`` (B calibrations), ``image_shape`` (B, 2) = (height, width), ``frame_id`` (B).  No host read."""
+        boxes, scores, labels, num = self._checked(out)
+        B = scores.shape[0]
+        calibs, shapes, ids = batch_dict['calib'], batch_dict['image_shape'], batch_dict['frame_id']
+        if len(calibs) != B or len(shapes) != B or len(ids) != B:
+            raise ValueError(f"KittiDetections.update: {B} samples, {len(calibs)} calibrations, {len(shapes)} image shapes, {len(ids)} frame ids")
+        on_device = isinstance(shapes, torch.Tensor) and shapes.is_cuda          # an image_shape already uploaded is not read back
+        packed = np.stack([kitti_pack_calib(calibs[b], None if on_device else _host(shapes[b], np.int64)) for b in range(B)])
+        pinned = torch.from_numpy(packed).pin_memory()                           # one small H2D copy that does not wait for the device
+        at = self._append(boxes, scores, labels, num, ids)
+        calib = self._store['calib']
+        calib[at].copy_(pinned, non_blocking=True)
+        self._pinned.append(pinned)                                              # alive until the copy has run (``counts`` waits)
+        if on_device:
+            calib[at, 33:35].copy_(shapes[:, :2])
+        self._host_num.append(None if host_num is None else [int(v) for v in host_num])
 
     def _alpha_row(self, row):
         x, y, heading = float(np.float32(row[0])), float(np.float32(row[1])), float(np.float32(row[6]))
@@ -869,8 +931,7 @@ class KittiDetections:
                 self._counts = packed[:F].astype(np.int64)
                 self._first = packed[F:]
                 self._pinned = []
-            if self._counts.size and (self._counts.min() < 0 or self._counts.max() > self.rows):
-                raise ValueError(f"KittiDetections: a frame count outside 0 .. {self.rows}")
+            self._counts_in_range(self._counts)
         return self._counts
 
     def finish(self, classes=None):
@@ -1116,24 +1177,6 @@ def once_overlaps_enough(iou, threshold):
     return iou > threshold
 
 
-def _once_first_pass(ov, score, flag_gt, flag_pred, min_ov):
-    """``accumulate_scores`` on one frame: ov (G, P) -> the true positives' scores per GT row, -inf elsewhere."""
-    G, P = ov.shape
-    out, assigned = np.full(G, -np.inf, np.float32), np.zeros(P, bool)
-    live = (flag_pred != -1) & (score > -1)                          # the reference's sentinel: a score at or below -1 never matches
-    for g in range(G):
-        if flag_gt[g] == -1:
-            continue
-        cand = live & ~assigned & once_overlaps_enough(ov[g], min_ov)
-        if not cand.any():
-            continue
-        j = int(np.argmax(np.where(cand, score, -np.inf)))          # the highest score; among equal scores the lowest index
-        assigned[j] = True
-        if not (flag_gt[g] == 1 or flag_pred[j] == 1):
-            out[g] = score[j]
-    return out
-
-
 def once_get_thresholds(scores_desc, num_gt, num_pr_points):
     """The score thresholds of one combo from its true positives' scores in descending order: the fp64 operations of the reference's
     ``get_thresholds`` in its order (csrc/once_eval.hip ``k_oe_thresholds`` is the same loop).  The true positive of rank r reaches
@@ -1162,34 +1205,9 @@ def once_false_positives(kept, flag_pred, assigned):
     return (kept & (flag_pred == 0)[None, :] & ~assigned).sum(axis=1).astype(np.int64)
 
 
-def _once_second_pass(ov, score, flag_gt, flag_pred, min_ov, thresholds):
-    """``compute_statistics`` on one frame for all T thresholds at once -> tp, fp, fn (T) int64.  Per GT row the reference's loop over
-    the predictions ends with the flag-0 candidate of the largest IoU (the first of equals), and only without one with the FIRST
-    flag-1 candidate."""
-    G, P = ov.shape
-    T = len(thresholds)
-    keep = ~(score[None, :] < np.asarray(thresholds, np.float32)[:, None])
-    c0, c1 = keep & (flag_pred == 0)[None, :], keep & (flag_pred == 1)[None, :]
-    assigned = np.zeros((T, P), bool)
-    tp, fn, rows = np.zeros(T, np.int64), np.zeros(T, np.int64), np.arange(T)
-    for g in range(G):
-        if flag_gt[g] == -1:
-            continue
-        if P == 0:
-            fn += int(flag_gt[g] == 0)
-            continue
-        over = once_overlaps_enough(ov[g], min_ov)[None, :]
-        m0 = c0 & ~assigned & over
-        has0 = m0.any(axis=1)
-        j0 = np.argmax(np.where(m0, ov[g][None, :], -1.0), axis=1)
-        m1 = c1 & ~assigned & over
-        has1 = m1.any(axis=1) & ~has0
-        j = np.where(has0, j0, np.argmax(m1, axis=1))
-        found = has0 | has1
-        if flag_gt[g] == 0:
-            fn += ~found
-        assigned[rows[found], j[found]] = True
-        tp += has0 & (flag_gt[g] == 0)
+def _once_second_pass(ov, enough, score, flag_gt, flag_pred, thresholds):
+    """``_second_pass`` on one frame's (G, P) overlaps -> tp, fp, fn (T) int64"""
+    tp, fn, keep, assigned, _ = _second_pass(ov, enough, score, flag_gt, flag_pred, thresholds)
     return tp, once_false_positives(keep, flag_pred, assigned), fn
 
 
@@ -1270,15 +1288,16 @@ def once_eval_numpy(gt_annos, pred_annos, classes, use_superclass=True, iou_thre
     thresholds, n_thr, counts = np.zeros((K, slots), np.float32), np.zeros(K, np.int64), np.zeros((K, slots, 3), np.int64)
     for k in range(K):
         mn = thr[k // B]
+        enough = [once_overlaps_enough(o, mn) for o in overlaps]
         for f in range(F):
-            matched[k, go[f]:go[f + 1]] = _once_first_pass(overlaps[f], score[po[f]:po[f + 1]], fg[k, go[f]:go[f + 1]],
-                                                           fp_[k, po[f]:po[f + 1]], mn)
+            matched[k, go[f]:go[f + 1]] = _first_pass(enough[f], score[po[f]:po[f + 1]], fg[k, go[f]:go[f + 1]], fp_[k, po[f]:po[f + 1]],
+                                                      -1)                 # the reference's sentinel
         tps = np.sort(matched[k][matched[k] > -np.inf])[::-1]
         th = once_get_thresholds(tps, int(num_valid[k]), num_pr_points)
         n = n_thr[k] = len(th)
         thresholds[k, :n] = th
         for f in range(F):
-            tp, fp, fn = _once_second_pass(overlaps[f], score[po[f]:po[f + 1]], fg[k, go[f]:go[f + 1]], fp_[k, po[f]:po[f + 1]], mn, th)
+            tp, fp, fn = _once_second_pass(overlaps[f], enough[f], score[po[f]:po[f + 1]], fg[k, go[f]:go[f + 1]], fp_[k, po[f]:po[f + 1]], th)
             counts[k, :n, 0] += tp
             counts[k, :n, 1] += fp
             counts[k, :n, 2] += fn
@@ -1291,7 +1310,7 @@ def once_eval_numpy(gt_annos, pred_annos, classes, use_superclass=True, iou_thre
                                    pred_off=po, classes=classes)
 
 
-class OnceEval:
+class OnceEval(_StagedEval):
     """The stages of ``once_eval`` as device tensors (csrc/once_eval.hip: five launches and one ``torch.sort`` between the two calls;
     no host read until ``curves``).  Boxes and SCORES are uploaded as fp32 and compared as fp32 values; an overlap is an fp32 value
     that is widened to fp64 against the class threshold.  The host only maps names to codes: the flags are the device's.
@@ -1321,14 +1340,10 @@ class OnceEval:
         else:
             pred_names = [_once_names(a) for a in pred_annos]
             po = _offsets([len(n) for n in pred_names])
-        for what, off in (("GT rows", go), ("predictions", po)):
-            if self.F and int(np.diff(off).max()) > ONCE_MAX_ROWS:
-                raise ValueError(f"once_eval: a frame with {int(np.diff(off).max())} {what} (at most {ONCE_MAX_ROWS})")
-        self.gt_off, self.pred_off = go, po
-        self.pair_off = _offsets(np.diff(go) * np.diff(po))
-        self.NG, self.ND, self.NP = int(go[-1]), int(po[-1]), int(self.pair_off[-1])
+        self.gt_off, self.pred_off, self.device = go, po, device
+        self._frames("once_eval", ONCE_MAX_ROWS, go, po, "predictions")
         self._host = [np.ascontiguousarray(o, np.int32) for o in (go, po)]                    # kept alive: read by the entry point
-        up = lambda a, t: torch.from_numpy(np.ascontiguousarray(a, t)).to(device)      # noqa: E731
+        up, e = self._up, self._empty
         if record is not None:
             pred_side = list(record.compact(self.names))
         else:
@@ -1338,7 +1353,6 @@ class OnceEval:
         self._in = [up(o, np.int32) for o in self._host] + [up(self.pair_off, np.int64), up(once_boxes(gt_annos), np.float32), pred_box,
                                                             pred_score, up(once_codes_of(gt_names, self.names), np.int32), pred_code,
                                                             up(accept.view(np.int32), np.int32), up(thr, np.float64)]
-        e = lambda *s, dtype=torch.float32: torch.empty(*s, dtype=dtype, device=device)      # noqa: E731
         slots = ONCE_THRESHOLD_SLOTS
         self._overlaps, self._matched = e(self.NP), e(self.K, self.NG)
         self._flag_gt, self._flag_pred = e(self.C, self.B, self.NG, dtype=torch.int8), e(self.C, self.B, self.ND, dtype=torch.int8)
@@ -1351,12 +1365,7 @@ class OnceEval:
             self._num_valid.zero_(), self._thresholds.zero_(), self._n_thr.zero_(), self._counts.zero_()
             self._sorted = self._matched
             return
-        with torch.cuda.device(device):
-            ws_bytes = L.load().gdmae_once_eval_workspace_bytes(self.F, self.K)
-            ws = e(max(ws_bytes, 1), dtype=torch.uint8)
-            self._call(L, 1, None, None, 0)
-            self._sorted = torch.sort(self._matched, dim=1, descending=True).values.contiguous()
-            self._call(L, 2, self._sorted, ws, ws_bytes)
+        self._run(L, L.load().gdmae_once_eval_workspace_bytes)
 
     def _call(self, L, stage, sorted_scores, ws, ws_bytes):
         L.call("gdmae_once_eval", stage, self.F, self.C, self._mode, self.num_pr_points, self._heading,
@@ -1425,83 +1434,39 @@ def once_annos_template(n=0):
     return {'name': np.zeros(n), 'score': np.zeros(n), 'boxes_3d': np.zeros((n, 7))}
 
 
-class OnceDetections:
+class OnceDetections(_DetectionStore):
     """The detections of an evaluation loop as a padded device store (``rows`` rows per frame, frames grown by doubling).  ``update``
     makes no host read; ``counts`` makes the one host read; ``compact`` and ``to_annos`` index with offsets built on the host."""
 
+    MAX_ROWS, ALLOC = ONCE_MAX_ROWS, staticmethod(torch.zeros)
+    CPU_DEVICE = "a device store; once_prediction_dicts is the CPU path"
+    CPU_TENSORS = "once_prediction_dicts is the CPU path"
+
     def __init__(self, class_names, device, rows=500, frames=0):
-        self.class_names = [str(c) for c in class_names]
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise NotImplementedError("OnceDetections: CPU device (a device store; once_prediction_dicts is the CPU path)")
-        if not 1 <= rows <= ONCE_MAX_ROWS:
-            raise ValueError(f"OnceDetections: rows {rows} (1 .. {ONCE_MAX_ROWS})")
+        super().__init__(class_names, device, rows)
         if not self.class_names:
             raise ValueError("OnceDetections: no class names")
-        self.rows, self.F, self.frame_ids = int(rows), 0, []
-        self._cap, self._store = 0, None
         self._reserve(int(frames))
-        self._counts = self._annos = self._index = None
+        self._invalidate()
 
-    def _reserve(self, need):
-        if need <= self._cap:
-            return
-        cap = self._cap
-        while cap < need:
-            cap = max(2 * cap, 1)
-        e = lambda *s, dtype=torch.float32: torch.zeros(*s, dtype=dtype, device=self.device)      # noqa: E731
-        new = dict(boxes=e(cap, self.rows, 7), scores=e(cap, self.rows), labels=e(cap, self.rows, dtype=torch.int64),
-                   num=e(cap, dtype=torch.int32))
-        if self._store is not None and self.F:
-            for k, t in new.items():
-                t[:self.F].copy_(self._store[k][:self.F])
-        self._cap, self._store = cap, new
-
-    def widen(self, rows):
-        """Reallocates the store with ``rows`` (> the present) rows per frame and copies what it holds: device copies, no host read."""
-        if not self.rows < rows <= ONCE_MAX_ROWS:
-            raise ValueError(f"OnceDetections.widen: rows {rows} ({self.rows + 1} .. {ONCE_MAX_ROWS})")
-        old, old_rows = self._store, self.rows
-        self.rows, self._cap, self._store = int(rows), 0, None
-        self._reserve(max(self.F, 1 if old is None else old['num'].shape[0]))
-        if old is not None and self.F:
-            for k in ('boxes', 'scores', 'labels'):
-                self._store[k][:self.F, :old_rows].copy_(old[k][:self.F])
-            self._store['num'][:self.F].copy_(old['num'][:self.F])
+    def _invalidate(self):
         self._counts = self._annos = self._index = None
 
     def update(self, out, batch_dict=None):
         """out: the padded dict of ``detect`` (pred_boxes (B, n, >= 7), pred_scores (B, n), pred_labels (B, n), num (B)); batch_dict:
         ``frame_id`` (B), optional.  No host read."""
-        boxes, scores, labels, num = out['pred_boxes'], out['pred_scores'], out['pred_labels'], out['num']
-        if boxes.dim() != 3 or boxes.shape[2] < 7 or tuple(scores.shape) != tuple(boxes.shape[:2]) or tuple(labels.shape) != tuple(
-                boxes.shape[:2]) or tuple(num.shape) != (boxes.shape[0],):
-            raise ValueError("OnceDetections.update: pred_boxes (B, n, >= 7), pred_scores / pred_labels (B, n), num (B)")
-        B, n = scores.shape
-        if n > self.rows:
-            raise ValueError(f"OnceDetections.update: n {n} rows per sample in a store of rows {self.rows}")
-        if not all(t.is_cuda for t in (boxes, scores, labels, num)):
-            raise NotImplementedError("OnceDetections.update: CPU tensors (once_prediction_dicts is the CPU path)")
+        boxes, scores, labels, num = self._checked(out)
+        B = scores.shape[0]
         ids = list(batch_dict['frame_id']) if batch_dict is not None and 'frame_id' in batch_dict else list(range(self.F, self.F + B))
         if len(ids) != B:
             raise ValueError(f"OnceDetections.update: {B} samples, {len(ids)} frame ids")
-        self._reserve(self.F + B)
-        s, at = self._store, slice(self.F, self.F + B)
-        if n:
-            s['boxes'][at, :n].copy_(boxes[..., :7])
-            s['scores'][at, :n].copy_(scores)
-            s['labels'][at, :n].copy_(labels)
-        s['num'][at].copy_(num)
-        self.frame_ids += ids
-        self.F += B
-        self._counts = self._annos = self._index = None
+        self._append(boxes, scores, labels, num, ids)
 
     def counts(self):
         """(F) int64 per-frame counts on the host: THE host read (cached until the next ``update``)."""
         if self._counts is None:
             self._counts = self._store['num'][:self.F].cpu().numpy().astype(np.int64) if self.F else np.zeros(0, np.int64)
-            if self._counts.size and (self._counts.min() < 0 or self._counts.max() > self.rows):
-                raise ValueError(f"OnceDetections: a frame count outside 0 .. {self.rows}")
+            self._counts_in_range(self._counts)
         return self._counts
 
     def _rows_index(self):

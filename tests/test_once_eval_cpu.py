@@ -128,6 +128,26 @@ def test_a_wrong_rule_moves_the_golden_table(mutation, monkeypatch):
     assert moved >= 0.5 and bad_str != ret_str
 
 
+def test_both_evaluators_match_by_one_rule():
+    """There is one matching rule: on a frame of each golden scene, with the same flags on both sides and no DontCare box, the second
+    pass gives the same tp / fp / fn through the KITTI wrapper ((D, G) overlaps, the bound inside) and through the ONCE one."""
+    import kitti_eval_reference as kk
+    kg, kd = kk.unpack_annos(np.load(os.path.join(os.path.dirname(GOLDEN), "kitti_eval.npz")))
+    _, og, op = golden()
+    frames = [(kk.frame_overlaps(kg[0], kd[0])[0][2].T, kd[0]['score']),
+              (evaluation.once_statement_overlaps(og[0]['boxes_3d'], op[0]['boxes_3d'], True, kr.bev_overlap), op[0]['score'])]
+    for ov, score in frames:
+        G, P = ov.shape
+        score = np.asarray(score, np.float32)
+        flag_gt, flag_pred = (np.where(i % 4 == 3, 1, np.where(i % 5 == 4, -1, 0)).astype(np.int8) for i in (np.arange(G), np.arange(P)))
+        thresholds = np.sort(score)[::-1][::max(P // 6, 1)]
+        for min_ov in (0.25, 0.5):
+            tp, fp, fn, _ = evaluation._kitti_second_pass(ov.T, score, None, None, flag_gt, flag_pred, None, min_ov, thresholds, False)
+            once = evaluation._once_second_pass(ov, evaluation.once_overlaps_enough(ov, min_ov), score, flag_gt, flag_pred, thresholds)
+            assert all(np.array_equal(a, b) for a, b in zip((tp, fp, fn), once))
+            assert tp.sum() > 0 and fp.sum() > 0 and fn.sum() > 0 and len(thresholds) > 3
+
+
 def test_options_and_refusals():
     _, g, p = golden()
     with pytest.raises(AssertionError, match="Car/Bus/Truck must all exist"):
