@@ -21,6 +21,13 @@ struct GtParams {
   int K;
 };
 
+// The one definition of a target: slot k of a pillar with cnt points takes its point k (first cnt by list order, then cyclic), relative
+// to the pillar centre (idx + 0.5) * vs + lo per axis, one rounding per operation in the reference's order.
+__device__ __forceinline__ int gt_slot(int k, int cnt) { return k < cnt ? k : k % cnt; }
+__device__ __forceinline__ float gt_centre(long long idx, float vs, float lo) {
+  return __fadd_rn(__fmul_rn(__fadd_rn((float)idx, 0.5f), vs), lo);
+}
+
 __global__ __launch_bounds__(256) void k_group_gt(const float* __restrict__ pts, const int* __restrict__ pt_off,
                                                   const int* __restrict__ csr, const long long* __restrict__ voxel_coords,
                                                   int M, GtParams P, float* __restrict__ gt, int* __restrict__ gidx) {
@@ -30,12 +37,11 @@ __global__ __launch_bounds__(256) void k_group_gt(const float* __restrict__ pts,
     const int off = pt_off[p];
     const int cnt = pt_off[p + 1] - off;
     const long long* vc = voxel_coords + 4ll * p;  // b, z, y, x
-    // centre = (idx + 0.5) * vs + lo per axis, reference op order
-    const float cx = __fadd_rn(__fmul_rn(__fadd_rn((float)vc[3], 0.5f), P.vs[0]), P.lo[0]);
-    const float cy = __fadd_rn(__fmul_rn(__fadd_rn((float)vc[2], 0.5f), P.vs[1]), P.lo[1]);
-    const float cz = __fadd_rn(__fmul_rn(__fadd_rn((float)vc[1], 0.5f), P.vs[2]), P.lo[2]);
+    const float cx = gt_centre(vc[3], P.vs[0], P.lo[0]);
+    const float cy = gt_centre(vc[2], P.vs[1], P.lo[1]);
+    const float cz = gt_centre(vc[1], P.vs[2], P.lo[2]);
     for (int k = lane; k < P.K; k += GD_WAVE) {
-      const int src = k < cnt ? k : k % cnt;
+      const int src = gt_slot(k, cnt);
       const int pid = csr[off + src];
       const float* r = pts + (long long)pid * P.ncols;
       float* o = gt + ((long long)p * P.K + k) * 3;
@@ -158,9 +164,16 @@ __device__ __forceinline__ void ch_tstep(unsigned long long (&k)[16], int mask, 
   }
 }
 
+// POINTS = true (gdmae_chamfer_points): the (M, P2, 3) targets are never written.  Lane j takes target j of k_group_gt itself,
+// points[pillar_pts[off + gt_slot(j, cnt)]] - centre: a pillar has ~11 points, so the array was a ~6-fold replication of them, written
+// for the visible pillars too.  Offset, index and point loads are unconditional with a clamped slot (a branch around a load is a join
+// with a load in flight); lanes >= P2 are cleared afterwards.  A zero-weight pillar leaves before any of them.
+template <bool POINTS>
 __global__ __launch_bounds__(256) void k_chamfer16(const float* __restrict__ pred, const float* __restrict__ gt,
-                                                   const float* __restrict__ w, int M, int P2, float* __restrict__ term,
-                                                   float* __restrict__ dpred) {
+                                                   const float* __restrict__ pts, const int* __restrict__ pt_off,
+                                                   const int* __restrict__ csr, const long long* __restrict__ voxel_coords,
+                                                   GtParams G, const float* __restrict__ w, int M, int P2,
+                                                   float* __restrict__ term, float* __restrict__ dpred) {
   __shared__ float sx[4][48];
   __shared__ float sy[4][GD_WAVE * 3];
   __shared__ int sb[4][GD_WAVE];
@@ -179,7 +192,20 @@ __global__ __launch_bounds__(256) void k_chamfer16(const float* __restrict__ pre
     if (lane < 48) sx[wib][lane] = pred[(long long)m * 48 + lane];
     const bool has = lane < P2;
     float y0 = 0.f, y1 = 0.f, y2 = 0.f;
-    if (has) {
+    if (POINTS) {
+      const int off = pt_off[m];
+      const int cnt = pt_off[m + 1] - off;
+      const long long* vc = voxel_coords + 4ll * m;  // b, z, y, x
+      const int pid = csr[off + gt_slot(has ? lane : P2 - 1, cnt)];
+      const float* r = pts + (long long)pid * G.ncols;
+      const float r1 = r[1], r2 = r[2], r3 = r[3];
+      const float t0 = __fsub_rn(r1, gt_centre(vc[3], G.vs[0], G.lo[0]));
+      const float t1 = __fsub_rn(r2, gt_centre(vc[2], G.vs[1], G.lo[1]));
+      const float t2 = __fsub_rn(r3, gt_centre(vc[1], G.vs[2], G.lo[2]));
+      y0 = has ? t0 : 0.f;
+      y1 = has ? t1 : 0.f;
+      y2 = has ? t2 : 0.f;
+    } else if (has) {
       const float* g = gt + ((long long)m * P2 + lane) * 3;
       y0 = g[0];
       y1 = g[1];
@@ -222,9 +248,18 @@ __global__ __launch_bounds__(256) void k_chamfer16(const float* __restrict__ pre
     const float sumx = gd_wave_sum((lane & 3) == 0 ? dmin : 0.f);
     const float sumy = gd_wave_sum(has ? best : 0.f);
     if (lane == 0) term[m] = cx * sumx + cy * sumy;
-    sy[wib][3 * lane] = y0;
-    sy[wib][3 * lane + 1] = y1;
-    sy[wib][3 * lane + 2] = y2;
+    if (POINTS) {
+      // column term, once per ground-truth point: lane j leaves 2 cy (x_besti - y_j) where the loop below would have formed it for
+      // the one prediction i = besti that keeps it - the same operands and operations (no contraction in this build), so the 48
+      // lanes only pick and add.  The two-launch entry keeps the loop it always had, and the tests hold the two against each other.
+      sy[wib][3 * lane] = 2.f * cy * (sx[wib][3 * besti] - y0);
+      sy[wib][3 * lane + 1] = 2.f * cy * (sx[wib][3 * besti + 1] - y1);
+      sy[wib][3 * lane + 2] = 2.f * cy * (sx[wib][3 * besti + 2] - y2);
+    } else {
+      sy[wib][3 * lane] = y0;
+      sy[wib][3 * lane + 1] = y1;
+      sy[wib][3 * lane + 2] = y2;
+    }
     sb[wib][lane] = has ? besti : -1;
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     __builtin_amdgcn_wave_barrier();
@@ -233,7 +268,7 @@ __global__ __launch_bounds__(256) void k_chamfer16(const float* __restrict__ pre
       const float xi = sx[wib][lane];
       float acc = 0.f;
       for (int j = 0; j < P2; ++j) {
-        const float v = 2.f * cy * (xi - sy[wib][3 * j + c]);
+        const float v = POINTS ? sy[wib][3 * j + c] : 2.f * cy * (xi - sy[wib][3 * j + c]);
         acc += sb[wib][j] == i ? v : 0.f;
       }
       dp[lane] = sg[wib][lane] + acc;
@@ -250,10 +285,34 @@ extern "C" int gdmae_chamfer(const float* pred, const float* gt, const float* we
   int grid = gd_div_up(M, 4);
   if (grid > 8192) grid = 8192;
   if (P1 == 16)
-    hipLaunchKernelGGL(k_chamfer16, dim3(grid), dim3(256), 0, (hipStream_t)stream, pred, gt, weights, M, P2, term, dpred);
+    hipLaunchKernelGGL(k_chamfer16<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, pred, gt, nullptr, nullptr, nullptr, nullptr,
+                       GtParams{}, weights, M, P2, term, dpred);
   else
     hipLaunchKernelGGL((k_chamfer<64>), dim3(grid), dim3(256), 0, (hipStream_t)stream, pred, gt, weights, M, P1, P2, term,
                        dpred);
+  GD_LAUNCH_CHECK();
+  return 0;
+}
+
+// gdmae_group_gt_points(K = P2) -> gdmae_chamfer(P1 = 16) as one launch, bit for bit, without the (M, P2, 3) targets in between
+extern "C" int gdmae_chamfer_points(const float* pred, const float* points, int n_cols, const int* pillar_pt_off, const int* pillar_pts,
+                                    const long long* voxel_coords, const float* lo, const float* vs, const float* weights, int M,
+                                    int P1, int P2, float* term, float* dpred, void* stream) {
+  if (M <= 0) return 0;
+  GD_REQUIRE(P1 == 16, "chamfer_points serves NUM_PRD_POINTS = 16 (gdmae_group_gt_points + gdmae_chamfer for the others)");
+  GD_REQUIRE(P2 >= 1 && P2 <= GD_WAVE, "NUM_GT_POINTS must be <= 64 (one lane per ground-truth point)");
+  GD_REQUIRE(n_cols >= 4, "point rows are (b, x, y, z, ...)");
+  GtParams G;
+  for (int i = 0; i < 3; ++i) {
+    G.lo[i] = lo[i];
+    G.vs[i] = vs[i];
+  }
+  G.ncols = n_cols;
+  G.K = P2;
+  int grid = gd_div_up(M, 4);
+  if (grid > 8192) grid = 8192;
+  hipLaunchKernelGGL(k_chamfer16<true>, dim3(grid), dim3(256), 0, (hipStream_t)stream, pred, nullptr, points, pillar_pt_off, pillar_pts,
+                     voxel_coords, G, weights, M, P2, term, dpred);
   GD_LAUNCH_CHECK();
   return 0;
 }

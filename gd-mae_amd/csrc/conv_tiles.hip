@@ -673,6 +673,53 @@ extern "C" int gdmae_tiles_gather_rows(const void* Yc, const int* tile_slot, con
   return 0;
 }
 
+// The bf16 gather with BatchNorm + ReLU of the gathered rows in the same pass: yrows[i] = Y row of cell[i] (kept: the backward's
+// statistics read it), out[i] = relu(fmaf(a, y, b)) in fp32 - the arithmetic of k_rows_affine_relu_scatter_v8 on those rows.
+__global__ __launch_bounds__(256) void k_tiles_gather_rows_affine_relu(const void* __restrict__ Yc, GdTiles T, const int* __restrict__ cell,
+                                                                       long long n, int H, int W, int C, const float* __restrict__ a,
+                                                                       const float* __restrict__ b, uint4* __restrict__ yrows,
+                                                                       float4* __restrict__ out) {
+  const int cv = C / 8;
+  const long long total = n * cv;
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+    const long long r = total < (1ll << 31) ? (long long)((unsigned)i / (unsigned)cv) : i / cv;
+    const int v = (int)(i - r * cv);
+    const int s = cell[r];
+    const int x = s % W, q = s / W, y = q % H, bb = q / H;
+    const uint4 yq = ((const uint4*)gd_y_row<2>(Yc, T, bb, y, x, H, W, C))[v];
+    const float4 a0 = ((const float4*)a)[2 * v], a1 = ((const float4*)a)[2 * v + 1];
+    const float4 b0 = ((const float4*)b)[2 * v], b1 = ((const float4*)b)[2 * v + 1];
+    const unsigned w4[4] = {yq.x, yq.y, yq.z, yq.w};
+    const float av[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
+    const float bv[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
+    float o[8];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float h0 = fmaf(av[2 * j], __uint_as_float(w4[j] << 16), bv[2 * j]);
+      const float h1 = fmaf(av[2 * j + 1], __uint_as_float(w4[j] & 0xFFFF0000u), bv[2 * j + 1]);
+      o[2 * j] = h0 > 0.f ? h0 : 0.f;
+      o[2 * j + 1] = h1 > 0.f ? h1 : 0.f;
+    }
+    yrows[i] = yq;
+    out[2 * i] = make_float4(o[0], o[1], o[2], o[3]);
+    out[2 * i + 1] = make_float4(o[4], o[5], o[6], o[7]);
+  }
+}
+
+extern "C" int gdmae_tiles_gather_rows_affine_relu(const void* Yc, const int* tile_slot, const void* ybg, const int* cell, long long n,
+                                                   int H, int W, int C, const float* a, const float* b, void* yrows, float* out,
+                                                   void* stream) {
+  GD_REQUIRE(tile_slot != nullptr && C % 8 == 0 && a != nullptr && b != nullptr, "tiles_gather_rows_affine_relu: bf16 rows, C % 8 == 0");
+  if (n <= 0) return 0;
+  GdTiles T{tile_slot, ybg, (H + 7) / 8, (W + 7) / 8};
+  long long g = (n * (C / 8) + 255) / 256;
+  if (g > 16384) g = 16384;
+  hipLaunchKernelGGL(k_tiles_gather_rows_affine_relu, dim3((int)g), dim3(256), 0, (hipStream_t)stream, Yc, T, cell, n, H, W, C, a, b,
+                     (uint4*)yrows, (float4*)out);
+  GD_LAUNCH_CHECK();
+  return 0;
+}
+
 // dense (B*H*W, C) copy of the tile-compact map (only for callers that ask for the reference's dense spatial_features)
 template <int ES>
 __global__ __launch_bounds__(256) void k_tiles_to_dense(const void* __restrict__ Yc, GdTiles T, int B, int H, int W, int C,

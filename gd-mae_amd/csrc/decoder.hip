@@ -741,10 +741,14 @@ extern "C" int gdmae_conv3x3_grad_taps(const void* Ymap, int y_bf16, const int* 
 // blocks = four wavefronts each, one wavefront per (chunk of the pillar list, region) doing a ballot scan.
 // ------------------------------------------------------------------------------------------
 #define DEC_BORDER_CHUNKS 64
-template <bool BF>
+// FUSED (gdmae_border_sums_rows): `rows` holds the output gradient of the pillar rows (dout) and a border pillar's row is formed on
+// the spot from it and the conv output at the pillar site (yrows, in Y's dtype), as k_decoder_dy<true> does; same chunks, same order.
+template <bool BF, bool FUSED>
 __global__ __launch_bounds__(256) void k_border_partial(const void* __restrict__ Y, GdTiles T, const float* __restrict__ rows,
-                                                        const int* __restrict__ pillar_cell, int M, int B, int H, int W, int C,
-                                                        float* __restrict__ part_edge, float* __restrict__ part_rows) {
+                                                        const void* __restrict__ yrows, const float* __restrict__ a2,
+                                                        const float* __restrict__ b2, const int* __restrict__ pillar_cell, int M,
+                                                        int B, int H, int W, int C, float* __restrict__ part_edge,
+                                                        float* __restrict__ part_rows) {
   extern __shared__ float sh[];
   const int cv = C >> 3;
   if ((int)blockIdx.x < 4 * B) {
@@ -792,6 +796,15 @@ __global__ __launch_bounds__(256) void k_border_partial(const void* __restrict__
   const int per = ((M + DEC_BORDER_CHUNKS - 1) / DEC_BORDER_CHUNKS + 63) / 64 * 64;
   const int pb = chunk * per, pe = pb + per < M ? pb + per : M;
   float acc[4] = {0.f, 0.f, 0.f, 0.f};                                   // C <= 256
+  float av[4] = {0.f, 0.f, 0.f, 0.f}, bv[4] = {0.f, 0.f, 0.f, 0.f};
+  if (FUSED) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (lane + 64 * j < C) {
+        av[j] = a2[lane + 64 * j];
+        bv[j] = b2[lane + 64 * j];
+      }
+  }
   for (int p0 = pb; p0 < pe; p0 += 64) {
     const int p = p0 + lane;
     bool in = false;
@@ -809,7 +822,15 @@ __global__ __launch_bounds__(256) void k_border_partial(const void* __restrict__
       const float* rp = rows + (long long)(p0 + k) * C;
 #pragma unroll
       for (int j = 0; j < 4; ++j)
-        if (lane + 64 * j < C) acc[j] += rp[lane + 64 * j];
+        if (lane + 64 * j < C) {
+          float v = rp[lane + 64 * j];
+          if (FUSED) {
+            const float y = dec_ld<BF>(yrows, (long long)(p0 + k) * C + lane + 64 * j);
+            const float dh = fmaf(av[j], y, bv[j]) > 0.f ? v : 0.f;
+            v = fmaf(av[j], dh, fmaf(0.f, y, 0.f));
+          }
+          acc[j] += v;
+        }
     }
   }
 #pragma unroll
@@ -841,22 +862,39 @@ extern "C" size_t gdmae_border_sums_workspace_bytes(int B, int C) {
   return (size_t)(4 * B + 8 * DEC_BORDER_CHUNKS) * C * sizeof(float);
 }
 
-extern "C" int gdmae_border_sums(const void* Y, int y_bf16, const int* tile_slot, const void* ybg, const float* rows,
-                                 const int* pillar_cell, int M, int B, int H, int W, int C, double* out /* [16][C] */,
-                                 void* workspace, void* stream) {
+static int border_sums(const void* Y, int y_bf16, const int* tile_slot, const void* ybg, const float* rows, const void* yrows,
+                       const float* a2, const float* b2, const int* pillar_cell, int M, int B, int H, int W, int C,
+                       double* out /* [16][C] */, void* workspace, void* stream) {
   const GdTiles T{tile_slot, ybg, (H + 7) / 8, (W + 7) / 8};
   GD_REQUIRE(C % 8 == 0 && C <= 256 && 256 % (C / 8) == 0, "border_sums: C in {64, 128, 256}");
   hipStream_t st = (hipStream_t)stream;
   float* part_edge = (float*)workspace;
   float* part_rows = part_edge + (size_t)4 * B * C;
   const size_t lds = (size_t)(256 / (C / 8)) * C * sizeof(float);
-  if (y_bf16) hipLaunchKernelGGL((k_border_partial<true>), dim3(4 * B + 2 * DEC_BORDER_CHUNKS), dim3(256), lds, st, Y, T, rows, pillar_cell, M, B, H, W, C, part_edge, part_rows);
-  else hipLaunchKernelGGL((k_border_partial<false>), dim3(4 * B + 2 * DEC_BORDER_CHUNKS), dim3(256), lds, st, Y, T, rows, pillar_cell, M, B, H, W, C, part_edge, part_rows);
+  const dim3 grid(4 * B + 2 * DEC_BORDER_CHUNKS);
+#define GD_LAUNCH(BF, FU) \
+  hipLaunchKernelGGL((k_border_partial<BF, FU>), grid, dim3(256), lds, st, Y, T, rows, yrows, a2, b2, pillar_cell, M, B, H, W, C, part_edge, part_rows)
+  if (y_bf16) { if (yrows) GD_LAUNCH(true, true); else GD_LAUNCH(true, false); }
+  else { if (yrows) GD_LAUNCH(false, true); else GD_LAUNCH(false, false); }
+#undef GD_LAUNCH
   GD_LAUNCH_CHECK();
   if (y_bf16) hipLaunchKernelGGL((k_border_final<true>), dim3(gd_div_up(8 * C, 256)), dim3(256), 0, st, Y, T, part_edge, part_rows, B, H, W, C, out);
   else hipLaunchKernelGGL((k_border_final<false>), dim3(gd_div_up(8 * C, 256)), dim3(256), 0, st, Y, T, part_edge, part_rows, B, H, W, C, out);
   GD_LAUNCH_CHECK();
   return 0;
+}
+extern "C" int gdmae_border_sums(const void* Y, int y_bf16, const int* tile_slot, const void* ybg, const float* rows,
+                                 const int* pillar_cell, int M, int B, int H, int W, int C, double* out /* [16][C] */,
+                                 void* workspace, void* stream) {
+  return border_sums(Y, y_bf16, tile_slot, ybg, rows, nullptr, nullptr, nullptr, pillar_cell, M, B, H, W, C, out, workspace, stream);
+}
+// the same sums with the pillar rows formed from dout (M, C) fp32, the conv output at the pillar sites yrows (M, C) in Y's dtype and
+// the folded affine a2, b2 of the output BatchNorm (workspace as gdmae_border_sums)
+extern "C" int gdmae_border_sums_rows(const void* Y, int y_bf16, const int* tile_slot, const void* ybg, const float* dout,
+                                      const void* yrows, const float* a2, const float* b2, const int* pillar_cell, int M, int B, int H,
+                                      int W, int C, double* out /* [16][C] */, void* workspace, void* stream) {
+  GD_REQUIRE(dout != nullptr && yrows != nullptr && a2 != nullptr && b2 != nullptr, "border_sums_rows: dout, yrows, a2 and b2 are required");
+  return border_sums(Y, y_bf16, tile_slot, ybg, dout, yrows, a2, b2, pillar_cell, M, B, H, W, C, out, workspace, stream);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -955,9 +993,15 @@ extern "C" int gdmae_decoder_region_algebra(const double* stats2, const float* a
 // launch with gathered rows (dw_grouped.hip) over that rulebook: every dY row is read through L2, nothing is materialised
 // nine-fold.  Same values as the taps (one bf16 rounding of dY), same tap convention k = (ky + 1) * 3 + (kx + 1).
 // ------------------------------------------------------------------------------------------
+// FUSED (gdmae_decoder_dy_rows): `rows` holds the output gradient of the pillar rows (dout) and the pillar's row is formed here,
+// rows[p] = a2 * (a2 * y + b2 > 0 ? dout[p] : 0) + (0 * y + 0): k_rows_bwd_v8 with c0 = c1 = 0 on P = the conv output at the site,
+// which this thread already holds (the pillar rows the forward keeps are a bit copy of those rows of Yc).  The inner fmaf(0, y, 0) is
+// kept: it is what makes the sum +0 where a2 * dh is -0.
+template <bool FUSED>
 __global__ __launch_bounds__(256) void k_decoder_dy(const unsigned short* __restrict__ Yc, const int* __restrict__ tile_list, int n_act,
                                                     const float* __restrict__ k0, const float* __restrict__ k1,
-                                                    const float* __restrict__ rows, const int* __restrict__ cell2pillar, int H, int W,
+                                                    const float* __restrict__ rows, const float* __restrict__ a2,
+                                                    const float* __restrict__ b2, const int* __restrict__ cell2pillar, int H, int W,
                                                     int TH, int TW, int C, unsigned short* __restrict__ dYc) {
   // index arithmetic in 32 bits (the launcher checks n_act * 64 * C / 8 < 2^31): a 64-bit division and remainder per 16 bytes are
   // emulated (~200 instructions) next to 16 bytes of traffic each way
@@ -991,7 +1035,19 @@ __global__ __launch_bounds__(256) void k_decoder_dy(const unsigned short* __rest
       const int p = cell2pillar[((long long)b * H + y) * W + x];
       if (p >= 0) {
         const float4 r0 = ((const float4*)rows)[((long long)p * C + c0) >> 2], r1 = ((const float4*)rows)[(((long long)p * C + c0) >> 2) + 1];
-        o[0] += r0.x; o[1] += r0.y; o[2] += r0.z; o[3] += r0.w; o[4] += r1.x; o[5] += r1.y; o[6] += r1.z; o[7] += r1.w;
+        float rv[8] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w};
+        if (FUSED) {
+          float av[8], bv[8];
+          dec_ld8<false>(a2, c0, av);
+          dec_ld8<false>(b2, c0, bv);
+#pragma unroll
+          for (int j = 0; j < 8; ++j) {
+            const float dh = fmaf(av[j], yv[j], bv[j]) > 0.f ? rv[j] : 0.f;
+            rv[j] = fmaf(av[j], dh, fmaf(0.f, yv[j], 0.f));
+          }
+        }
+#pragma unroll
+        for (int j = 0; j < 8; ++j) o[j] += rv[j];
       }
       q.x = dec_f2bf(o[0]) | ((unsigned)dec_f2bf(o[1]) << 16);
       q.y = dec_f2bf(o[2]) | ((unsigned)dec_f2bf(o[3]) << 16);
@@ -1001,17 +1057,29 @@ __global__ __launch_bounds__(256) void k_decoder_dy(const unsigned short* __rest
     reinterpret_cast<uint4*>(dYc + row * C)[v] = q;
   }
 }
-extern "C" int gdmae_decoder_dy(const void* Yc, const int* tile_list, int n_act, const float* k0, const float* k1, const float* rows,
-                                const int* cell2pillar, int H, int W, int C, void* dYc, void* stream) {
+static int decoder_dy(const void* Yc, const int* tile_list, int n_act, const float* k0, const float* k1, const float* rows, const float* a2,
+                      const float* b2, const int* cell2pillar, int H, int W, int C, void* dYc, void* stream) {
   GD_REQUIRE(C % 8 == 0, "decoder_dy: C must be a multiple of 8");
   if (n_act <= 0) return 0;
   GD_REQUIRE((long long)n_act * GD_TILE_SITES * (C / 8) < (1ll << 31), "decoder_dy: active tiles x 64 x C / 8 must fit 31 bits");
   long long g = ((long long)n_act * GD_TILE_SITES * (C / 8) + 255) / 256;
   if (g > 65536) g = 65536;
-  hipLaunchKernelGGL(k_decoder_dy, dim3((int)g), dim3(256), 0, (hipStream_t)stream, (const unsigned short*)Yc, tile_list, n_act, k0, k1, rows,
-                     cell2pillar, H, W, (H + 7) / 8, (W + 7) / 8, C, (unsigned short*)dYc);
+  if (a2) hipLaunchKernelGGL(k_decoder_dy<true>, dim3((int)g), dim3(256), 0, (hipStream_t)stream, (const unsigned short*)Yc, tile_list, n_act, k0,
+                             k1, rows, a2, b2, cell2pillar, H, W, (H + 7) / 8, (W + 7) / 8, C, (unsigned short*)dYc);
+  else hipLaunchKernelGGL(k_decoder_dy<false>, dim3((int)g), dim3(256), 0, (hipStream_t)stream, (const unsigned short*)Yc, tile_list, n_act, k0,
+                          k1, rows, a2, b2, cell2pillar, H, W, (H + 7) / 8, (W + 7) / 8, C, (unsigned short*)dYc);
   GD_LAUNCH_CHECK();
   return 0;
+}
+extern "C" int gdmae_decoder_dy(const void* Yc, const int* tile_list, int n_act, const float* k0, const float* k1, const float* rows,
+                                const int* cell2pillar, int H, int W, int C, void* dYc, void* stream) {
+  return decoder_dy(Yc, tile_list, n_act, k0, k1, rows, nullptr, nullptr, cell2pillar, H, W, C, dYc, stream);
+}
+extern "C" int gdmae_decoder_dy_rows(const void* Yc, const int* tile_list, int n_act, const float* k0, const float* k1, const float* dout,
+                                     const float* a2, const float* b2, const int* cell2pillar, int H, int W, int C, void* dYc,
+                                     void* stream) {
+  GD_REQUIRE(dout != nullptr && a2 != nullptr && b2 != nullptr, "decoder_dy_rows: dout, a2 and b2 are required");
+  return decoder_dy(Yc, tile_list, n_act, k0, k1, dout, a2, b2, cell2pillar, H, W, C, dYc, stream);
 }
 
 // nbr[t * 9 + k] = tile-compact row of site[t] - (ky - 1, kx - 1), -1 outside the map (or in a tile that is not active: cannot

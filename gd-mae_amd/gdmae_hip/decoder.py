@@ -29,6 +29,8 @@ Exact identities used (no approximation):
   "block" (upsampling stride 2 / 4): the same, with the weight gradient on token blocks (gdmae_decoder_block_dw, csrc/decoder_blocks.hip);
   "taps" (GDMAE_DEC_BWD=taps, and whatever the tile path does not serve): the 9 shifted dY rows of the active sites are gathered
   (gdmae_conv3x3_grad_taps) and two library GEMMs give the input-gradient rows and the weight gradient.
+  The M sparse rows, a2 * relu'(a2 y + b2) * dout, are an array only for "taps"; the other two form them where they are added
+  (gdmae_decoder_dy_rows, gdmae_border_sums_rows), from the conv output that thread holds anyway.
 
 Autograd: one hand-derived Function (DecoderHead) from the token-side deconvolution rows to the pillar rows.
 """
@@ -55,6 +57,11 @@ CONV_BWD = os.environ.get("GDMAE_DEC_BWD", "implicit")
 # stages with an upsampling stride of 2 / 4 in the "implicit" backward: "1" = the weight gradient on token blocks (csrc/decoder_blocks.hip:
 # each token's dY halo staged once, the Zd rows never written), "0" = the rulebook path for every stage (A/B runs)
 BLOCK_BWD = os.environ.get("GDMAE_DEC_BLOCK", "1")
+# "1" = the pillar rows of dY (a2 * relu' * dout) are formed inside gdmae_decoder_dy_rows / gdmae_border_sums_rows, which hold the conv
+# output of the site anyway; "0" = gdmae_rows_bwd writes them as an (M, C2) fp32 array first (A/B runs).  The "taps" schedule reads the array.
+DY_ROWS = os.environ.get("GDMAE_DEC_DY_ROWS", "1") != "0"
+# "1" = the tile path gathers the pillar rows and writes their BatchNorm + ReLU in one launch; "0" = gather, then a second pass over the rows
+GATHER_FUSED = os.environ.get("GDMAE_DEC_GATHER_FUSED", "1") != "0"
 
 
 # sparse_decoder(..., pre_conv_hook=callable): invoked once right before the decoder's tile convolution is launched (the one
@@ -151,7 +158,8 @@ class DecoderGeom:
 #   Z                  (R, Cin) materialised map (dense_map; None on tiles)
 #   tile_slot, ybg     tile -> slot of y2 and the 9 border-class constants outside the tiles (tiles; None on dense_map)
 #   bgz                (Cin,) value of every non-active site of the map
-_Forward = namedtuple("_Forward", "y2 yrows stats2 ab2 mv2 Z tile_slot ybg bgz")
+#   out                (M, C2) fp32 relu(a2 * yrows + b2) where the schedule wrote it with the gather (tiles, GATHER_FUSED), else None
+_Forward = namedtuple("_Forward", "y2 yrows stats2 ab2 mv2 Z tile_slot ybg bgz out", defaults=(None,))
 
 
 def _forward_tiles(geom, pre_conv_hook, conv_w, gamma2, beta2, pillar_cell, Ps, widths, ab_l, bn2):
@@ -184,9 +192,15 @@ def _forward_tiles(geom, pre_conv_hook, conv_w, gamma2, beta2, pillar_cell, Ps, 
                L.ptr(ab2), L.ptr(mv2), L.ptr(ws), L.stream())
     M = pillar_cell.numel()
     yrows = torch.empty(M, C2, dtype=cdt, device=dev)
-    L.call("gdmae_tiles_gather_rows", L.ptr(y2), L.ptr(dt.tile_slot), L.ptr(ybg), L.ptr(pillar_cell), M, H, W, C2, 2,
-           L.ptr(yrows), L.stream())
-    return _Forward(y2, yrows, stats2, ab2, mv2, None, dt.tile_slot, ybg, bgz)
+    out = None
+    if GATHER_FUSED:
+        out = torch.empty(M, C2, dtype=torch.float32, device=dev)
+        L.call("gdmae_tiles_gather_rows_affine_relu", L.ptr(y2), L.ptr(dt.tile_slot), L.ptr(ybg), L.ptr(pillar_cell), M, H, W, C2,
+               L.ptr(ab2), L.ptr(ab2[C2:]), L.ptr(yrows), L.ptr(out), L.stream())
+    else:
+        L.call("gdmae_tiles_gather_rows", L.ptr(y2), L.ptr(dt.tile_slot), L.ptr(ybg), L.ptr(pillar_cell), M, H, W, C2, 2,
+               L.ptr(yrows), L.stream())
+    return _Forward(y2, yrows, stats2, ab2, mv2, None, dt.tile_slot, ybg, bgz, out)
 
 
 def _forward_dense_map(geom, conv_w, gamma2, beta2, pillar_cell, sites, Ps, widths, ab_l, bn2):
@@ -255,8 +269,8 @@ def _saved(ctx) -> SimpleNamespace:
 
 
 def _bn2_backward(s, dout, R, direct):
-    """BatchNorm2d #2 (+ReLU) at the pillar rows: dY = k0 + k1*Y + rows[pillar sites], rows = a*dh.
-    -> (rows (M, C2) fp32, st2 f64[3 C2] column sums, k01 f32[2 C2], dgamma2, dbeta2)"""
+    """BatchNorm2d #2 (+ReLU) at the pillar rows: dY = k0 + k1*Y + rows[pillar sites], rows = a*dh (_pillar_rows).
+    -> (dout (M, C2) fp32 contiguous, st2 f64[3 C2] column sums, k01 f32[2 C2], dgamma2, dbeta2)"""
     yrows, ab2 = s.yrows, s.ab2
     M, C2 = yrows.shape
     dev = yrows.device
@@ -266,22 +280,33 @@ def _bn2_backward(s, dout, R, direct):
     L.call("gdmae_rows_bwd_stats", L.ptr(yrows), _bf(yrows), None, M, C2, L.ptr(ab2), L.ptr(ab2[C2:]), L.ptr(dout), 0, C2, 0,
            L.ptr(st2), L.ptr(ws), L.stream())
     dgamma2, dbeta2, k01 = gbn.bwd_coeffs(st2, 3, s.stats2, ab2, s.gamma2, R, None, direct)
-    zero = torch.zeros(2 * C2, dtype=torch.float32, device=dev)
-    rows = torch.empty(M, C2, dtype=torch.float32, device=dev)
+    return dout, st2, k01, dgamma2, dbeta2
+
+
+def _pillar_rows(s, dout):
+    """rows (M, C2) fp32 = a2 * (a2 * yrows + b2 > 0 ? dout : 0), the sparse part of dY as an array (for the schedules that read one)"""
+    yrows, ab2 = s.yrows, s.ab2
+    M, C2 = yrows.shape
+    zero = torch.zeros(2 * C2, dtype=torch.float32, device=yrows.device)
+    rows = torch.empty(M, C2, dtype=torch.float32, device=yrows.device)
     L.call("gdmae_rows_bwd", L.ptr(yrows), _bf(yrows), None, M, C2, L.ptr(ab2), L.ptr(ab2[C2:]), L.ptr(zero), L.ptr(zero[C2:]),
            L.ptr(dout), 0, C2, 0, L.ptr(rows), 0, L.stream())
-    return rows, st2, k01, dgamma2, dbeta2
+    return rows
 
 
-def _region_sums(s, rows, B, H, W):
+def _region_sums(s, rows, dout, B, H, W):
     """(16, C2) f64 sums of Y (0..7) and of the pillar rows (8..15) over border rows / border columns / corners (regions 1..8 of
-    _TAP_REGION; region 0, all sites, follows from the BatchNorm statistics)"""
+    _TAP_REGION; region 0, all sites, follows from the BatchNorm statistics).  rows None: the border pillars' rows are formed from dout."""
     y2 = s.y2
     C2 = y2.shape[1]
     reg = torch.empty(16, C2, dtype=torch.float64, device=y2.device)
     ws = torch.empty(L.load().gdmae_border_sums_workspace_bytes(B, C2), dtype=torch.uint8, device=y2.device)
-    L.call("gdmae_border_sums", L.ptr(y2), _bf(y2), L.ptr(s.tile_slot), L.ptr(s.ybg), L.ptr(rows), L.ptr(s.pillar_cell),
-           rows.shape[0], B, H, W, C2, L.ptr(reg), L.ptr(ws), L.stream())
+    if rows is None:
+        L.call("gdmae_border_sums_rows", L.ptr(y2), _bf(y2), L.ptr(s.tile_slot), L.ptr(s.ybg), L.ptr(dout), L.ptr(s.yrows), L.ptr(s.ab2),
+               L.ptr(s.ab2[C2:]), L.ptr(s.pillar_cell), dout.shape[0], B, H, W, C2, L.ptr(reg), L.ptr(ws), L.stream())
+    else:
+        L.call("gdmae_border_sums", L.ptr(y2), _bf(y2), L.ptr(s.tile_slot), L.ptr(s.ybg), L.ptr(rows), L.ptr(s.pillar_cell),
+               rows.shape[0], B, H, W, C2, L.ptr(reg), L.ptr(ws), L.stream())
     return reg
 
 
@@ -431,14 +456,18 @@ class DecoderHead(torch.autograd.Function):
         else:
             f = _forward_dense_map(geom, conv_w, gamma2, beta2, pillar_cell, sites, Ps, widths, ab_l, bns[k])
         M, C2 = f.yrows.shape
-        out = torch.empty(M, C2, dtype=torch.float32, device=f.yrows.device)
-        L.call("gdmae_rows_affine_relu_scatter", L.ptr(f.yrows), _bf(f.yrows), None, M, C2, L.ptr(f.ab2), L.ptr(f.ab2[C2:]), L.ptr(out), 0,
-               C2, 0, L.stream())
+        out = f.out
+        if out is None:
+            out = torch.empty(M, C2, dtype=torch.float32, device=f.yrows.device)
+            L.call("gdmae_rows_affine_relu_scatter", L.ptr(f.yrows), _bf(f.yrows), None, M, C2, L.ptr(f.ab2), L.ptr(f.ab2[C2:]), L.ptr(out), 0,
+                   C2, 0, L.stream())
         _save(ctx, sites=sites, Ps=Ps, ab_l=ab_l, stats_l=stats_l, gammas=[g.detach() for g in gammas], Z=f.Z, y2=f.y2, bgz=f.bgz,
               yrows=f.yrows, ab2=f.ab2, stats2=f.stats2, pillar_cell=pillar_cell, cell2pillar=cell2pillar, gamma2=gamma2.detach(),
               conv_w=conv_w.detach(), tile_slot=f.tile_slot, ybg=f.ybg)
         ctx.geom, ctx.widths = geom, widths
         ctx.native_region, ctx.stage_bwd = _backward_schedule(geom, conv_w, sites, Ps, widths, f)
+        # the pillar rows of dY stay unwritten when no stage reads them as an array ("taps" does, through gdmae_conv3x3_grad_taps)
+        ctx.dy_rows = DY_ROWS and C2 % 8 == 0 and all(sb != "taps" for sb in ctx.stage_bwd)
         ctx.direct = [gbn.direct_pair(g, be) for g, be in zip(gammas, betas)] + [gbn.direct_pair(gamma2, beta2)]
         ctx.direct_w = ops.direct_grad(conv_w)
         ctx.conv_param = conv_w        # the parameter object itself: the packed images of the backward are registered on its identity
@@ -454,8 +483,9 @@ class DecoderHead(torch.autograd.Function):
         R, k = B * H * W, len(widths)
         b = _saved(ctx)                      # the saved tensors by name; the steps below add what they share
         b.H, b.W, b.cdt, b.widths = H, W, geom.cdt, widths
-        b.rows, st2, b.k01, dgamma2, dbeta2 = _bn2_backward(b, dout, R, ctx.direct[k])
-        reg = _region_sums(b, b.rows, B, H, W)
+        dout, st2, b.k01, dgamma2, dbeta2 = _bn2_backward(b, dout, R, ctx.direct[k])
+        b.rows = None if ctx.dy_rows else _pillar_rows(b, dout)
+        reg = _region_sums(b, b.rows, dout, B, H, W)
         tap_region, cnt = _region_consts(reg.device, B, H, W)
         algebra = region_algebra_native if ctx.native_region else region_algebra_torch
         S, b.tot, b.dWk, b.Wd = algebra(b.stats2, b.ab2, st2, b.k01, reg, tap_region, cnt, R, b.conv_w, b.bgz, geom.cdt)
@@ -465,6 +495,8 @@ class DecoderHead(torch.autograd.Function):
             b.packed = packing.decoder_conv_packed(ctx.conv_param, widths, ctx.direct_w is not None)
             if b.packed is None:
                 stage_bwd = ["taps"] * k
+                if b.rows is None:
+                    b.rows = _pillar_rows(b, dout)
             else:
                 # the output gradient ONCE in Y's tile-compact layout, rulebooks of the (active site, tap) rows
                 b.tiles, b.ups = geom.tile_conv.tiles, geom.tile_conv.ups
@@ -472,8 +504,12 @@ class DecoderHead(torch.autograd.Function):
                     b.tiles.nbr = gplan.decoder_site_rulebooks(b.tiles, b.sites, b.ups)
                 C2 = b.y2.shape[1]
                 b.dYc = torch.empty_like(b.y2)
-                L.call("gdmae_decoder_dy", L.ptr(b.y2), L.ptr(b.tiles.tile_list), b.tiles.n_act, L.ptr(b.k01), L.ptr(b.k01[C2:]),
-                       L.ptr(b.rows), L.ptr(b.cell2pillar), H, W, C2, L.ptr(b.dYc), L.stream())
+                if b.rows is None:
+                    L.call("gdmae_decoder_dy_rows", L.ptr(b.y2), L.ptr(b.tiles.tile_list), b.tiles.n_act, L.ptr(b.k01), L.ptr(b.k01[C2:]),
+                           L.ptr(dout), L.ptr(b.ab2), L.ptr(b.ab2[C2:]), L.ptr(b.cell2pillar), H, W, C2, L.ptr(b.dYc), L.stream())
+                else:
+                    L.call("gdmae_decoder_dy", L.ptr(b.y2), L.ptr(b.tiles.tile_list), b.tiles.n_act, L.ptr(b.k01), L.ptr(b.k01[C2:]),
+                           L.ptr(b.rows), L.ptr(b.cell2pillar), H, W, C2, L.ptr(b.dYc), L.stream())
         grads = [None] * 8
         dW_rows = []
         col = 0

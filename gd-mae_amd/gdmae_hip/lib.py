@@ -73,6 +73,7 @@ SIGNATURES = {
     "gdmae_bn_bwd_coeffs_rows": (_I, [_P, _I, _I, _P, _P, _P, _I, _D, _P, _P, _P, _I, _P, _P]),
     "gdmae_border_sums_workspace_bytes": (_Z, [_I, _I]),
     "gdmae_border_sums": (_I, [_P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
+    "gdmae_border_sums_rows": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
     "gdmae_conv3x3_grad_taps": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _P, _P]),
     "gdmae_decoder_tiles_workspace_bytes": (_Z, [_I, _I, _I]),
     "gdmae_decoder_tiles": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
@@ -82,6 +83,7 @@ SIGNATURES = {
     "gdmae_conv3x3_tiles_fwd": (_I, [_P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _D, _D, _P, _P, _P, _P, _P, _P,
                                      _P, _P]),
     "gdmae_tiles_gather_rows": (_I, [_P, _P, _P, _P, _L, _I, _I, _I, _I, _P, _P]),
+    "gdmae_tiles_gather_rows_affine_relu": (_I, [_P, _P, _P, _P, _L, _I, _I, _I, _P, _P, _P, _P, _P]),
     "gdmae_tiles_to_dense": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P]),
     "gdmae_tiles_to_dense_affine_relu": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
     "gdmae_rows_bwd": (_I, [_P, _I, _P, _L, _I, _P, _P, _P, _P, _P, _I, _I, _I, _P, _I, _P]),
@@ -136,6 +138,7 @@ SIGNATURES = {
     "gdmae_spconv_stat_rows": (_I, [_I, _I, _I]),
     "gdmae_spconv_stats": (_I, [_P, _I, _P, _P, _L, _I, _I, _P, _P, _P]),
     "gdmae_decoder_dy": (_I, [_P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _P, _P]),
+    "gdmae_decoder_dy_rows": (_I, [_P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P]),
     "gdmae_decoder_site_rulebook": (_I, [_P, _P, _I, _L, _P, _I, _I, _P, _P]),
     "gdmae_tap_dw_rows": (_L, [_L, _I, _I]),
     "gdmae_tap_dw_workspace_bytes": (_Z, [_L, _I, _I]),
@@ -175,6 +178,7 @@ SIGNATURES = {
     "gdmae_encoder_stage_fused": (_I, [_P, _I]),
     "gdmae_group_gt_points": (_I, [_P, _I, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P]),
     "gdmae_chamfer": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P]),
+    "gdmae_chamfer_points": (_I, [_P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P]),
     "gdmae_augment_collate_workspace_bytes": (_Z, [_L]),
     "gdmae_augment_collate": (_I, [_P, _L, _I, _P, _I, _P, _P, _P, _P, _P, _P]),
     "gdmae_gt_sample_workspace_bytes": (_Z, [_L]),

@@ -6,6 +6,8 @@ libgdmae_hip.so.  There is no fallback path: without the library these ops raise
 """
 from __future__ import annotations
 
+import os
+
 import torch
 
 from . import lib as L
@@ -471,6 +473,51 @@ def group_gt_points(vox, K: int, want_index: bool = False):
     return (gt, gi) if want_index else gt
 
 
+# "1" = the Chamfer kernel takes its targets from the points (gdmae_chamfer_points: no (M, K, 3) array in between) where that entry
+# serves the call; "0" = gdmae_group_gt_points, then gdmae_chamfer (A/B runs)
+CHAMFER_POINTS = os.environ.get("GDMAE_CHAMFER_POINTS", "1") != "0"
+
+
+class LazyTargets:
+    """The (M, K, 3) reconstruction targets of a voxelization, not yet written: ChamferLoss hands the voxelization to
+    gdmae_chamfer_points instead; ``materialize()`` is group_gt_points(vox, K) for every other reader."""
+    __slots__ = ("vox", "K", "_gt")
+
+    def __init__(self, vox, K: int):
+        self.vox, self.K, self._gt = vox, int(K), None
+
+    @property
+    def shape(self):
+        return (self.vox.M, self.K, 3)
+
+    def materialize(self):
+        if self._gt is None:
+            self._gt = group_gt_points(self.vox, self.K)
+        return self._gt
+
+
+def chamfer_targets(vox, K: int, P1: int):
+    """The targets for ChamferLoss: lazy where gdmae_chamfer_points serves the loss (P1 = 16, K <= 64), the tensor otherwise."""
+    if CHAMFER_POINTS and P1 == 16 and 1 <= K <= 64 and vox.n_cols >= 4:
+        return LazyTargets(vox, K)
+    return group_gt_points(vox, K)
+
+
+class TargetDict(dict):
+    """forward_ret_dict of the MAE backbone: 'gt_points' may be held lazily; reading it by key gives the (M, K, 3) tensor (written on
+    first use).  ``raw('gt_points')`` gives what is stored."""
+
+    def raw(self, key):
+        return dict.__getitem__(self, key)
+
+    def __getitem__(self, key):
+        v = dict.__getitem__(self, key)
+        return v.materialize() if isinstance(v, LazyTargets) else v
+
+    def get(self, key, default=None):
+        return self[key] if key in self else default
+
+
 LAZY_SCALE = {}      # data_ptr of an UNSCALED fp32 Chamfer gradient -> (upstream gradient, 1 / sum of weights), consumed by the
                      # prediction head's backward (gdmae_hip.decoder.PredHeadFn), which applies the scale on load
 
@@ -486,12 +533,20 @@ class ChamferLoss(torch.autograd.Function):
     def forward(ctx, pred, gt, weights, lazy_scale=False):
         ctx.pred_dtype = pred.dtype       # bf16 rows of the prediction head under autocast: gradient returned in bf16
         ctx.lazy = bool(lazy_scale and pred.dtype == torch.float32)
-        pred, gt, weights = _f32c(pred.float()), _f32c(gt), _f32c(weights)
+        pred, weights = _f32c(pred.float()), _f32c(weights)
         M, P1, _ = pred.shape
-        P2 = gt.shape[1]
+        if isinstance(gt, LazyTargets) and not (P1 == 16 and gt.K <= 64 and gt.vox.M == M):
+            gt = gt.materialize()
         term = torch.empty(max(M, 1), dtype=torch.float32, device=pred.device)
         dpred = torch.empty_like(pred)
-        L.call("gdmae_chamfer", L.ptr(pred), L.ptr(gt), L.ptr(weights), M, P1, P2, L.ptr(term), L.ptr(dpred), L.stream())
+        if isinstance(gt, LazyTargets):
+            vox = gt.vox
+            L.call("gdmae_chamfer_points", L.ptr(pred), L.ptr(vox.points), vox.n_cols, L.ptr(vox.pt_off), L.ptr(vox.pillar_pts),
+                   L.ptr(vox.voxel_coords), L.host_f32(vox.lo), L.host_f32(vox.vs), L.ptr(weights), M, P1, gt.K, L.ptr(term), L.ptr(dpred),
+                   L.stream())
+        else:
+            gt = _f32c(gt)
+            L.call("gdmae_chamfer", L.ptr(pred), L.ptr(gt), L.ptr(weights), M, P1, gt.shape[1], L.ptr(term), L.ptr(dpred), L.stream())
         res = torch.empty(2, dtype=torch.float32, device=pred.device)       # {loss, 1 / sum of weights}
         L.call("gdmae_weighted_mean_finish", L.ptr(term), L.ptr(weights), M, L.ptr(res), L.stream())
         ctx.save_for_backward(dpred, res)

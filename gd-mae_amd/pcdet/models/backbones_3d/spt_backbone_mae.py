@@ -86,7 +86,9 @@ class SPTBackboneMAE(nn.Module):
         # head's own backward can see the gradient of pred_points: checked here, the scaled gradient otherwise
         pred = r['pred_points']
         lazy = bool(r.get('pred_lazy_scale', False)) and _only_the_pred_head_sees_the_gradient(pred)
-        return ops.ChamferLoss.apply(pred, r['gt_points'], r['mask'], lazy), tb_dict
+        # the targets as stored: where they are held lazily the Chamfer kernel takes them from the points (ops.LazyTargets)
+        gt = r.raw('gt_points') if isinstance(r, ops.TargetDict) else r['gt_points']
+        return ops.ChamferLoss.apply(pred, gt, r['mask'], lazy), tb_dict
 
     def forward(self, batch_dict):
         """Inputs: DynVFE's ``voxel_features`` + the voxel plan.  Optional ``mae_noise`` (M,) injects the
@@ -177,7 +179,9 @@ class SPTBackboneMAE(nn.Module):
 
     def target_assigner(self, batch_dict):
         vox = batch_dict['_gdmae_vox']
-        gt = ops.group_gt_points(vox, self.mask_cfg.NUM_GT_POINTS)         # (M, K, 3), centre-relative
+        # (M, K, 3), centre-relative; not written where the Chamfer kernel reads the points itself - whoever else asks for
+        # forward_ret_dict['gt_points'] gets the tensor
+        gt = ops.chamfer_targets(vox, self.mask_cfg.NUM_GT_POINTS, self.mask_cfg.NUM_PRD_POINTS)
         flat = gdec.pred_head(batch_dict['voxel_features'], self.decoder_pred)
-        return {'pred_points': flat.view(vox.M, -1, 3), 'gt_points': gt, 'mask': batch_dict['voxel_mae_mask'],
-                'pred_lazy_scale': bool(getattr(flat, '_gd_pred_head', False))}
+        return ops.TargetDict({'pred_points': flat.view(vox.M, -1, 3), 'gt_points': gt, 'mask': batch_dict['voxel_mae_mask'],
+                               'pred_lazy_scale': bool(getattr(flat, '_gd_pred_head', False))})

@@ -299,6 +299,11 @@ int gdmae_conv3x3_grad_taps(const void* Y, int y_bf16, const int* tile_slot, con
 size_t gdmae_border_sums_workspace_bytes(int B, int C);
 int gdmae_border_sums(const void* Y, int y_bf16, const int* tile_slot, const void* ybg, const float* rows,
                       const int* pillar_cell, int M, int B, int H, int W, int C, double* out, void* workspace, void* stream);
+/* The same sums with rows[p] formed in the launch from dout (M, C) fp32, yrows (M, C) = the conv output at the pillar sites in Y's
+ * dtype and the folded affine a2, b2, as gdmae_decoder_dy_rows forms it. */
+int gdmae_border_sums_rows(const void* Y, int y_bf16, const int* tile_slot, const void* ybg, const float* dout, const void* yrows,
+                           const float* a2, const float* b2, const int* pillar_cell, int M, int B, int H, int W, int C, double* out,
+                           void* workspace, void* stream);
 
 /* ---- decoder conv_out (Conv2d 3x3 pad 1, spt_backbone_mae.py:46-52,125-133) on the ACTIVE TILES of the BEV map --------
  * Replaces F.conv2d (MIOpen) + the dense 384-channel input map + the statistics pass over the dense output.
@@ -328,6 +333,9 @@ int gdmae_conv3x3_tiles_fwd(const void* const* P, const int* const* maps, const 
                             float* mv, void* workspace, void* stream);
 int gdmae_tiles_gather_rows(const void* Yc, const int* tile_slot, const void* ybg, const int* cell, long long n, int H, int W,
                             int C, int elem_bytes, void* out, void* stream);
+/* gdmae_tiles_gather_rows of a bf16 map that also writes out[i] = relu(a * yrows[i] + b) in fp32 (C % 8 == 0) */
+int gdmae_tiles_gather_rows_affine_relu(const void* Yc, const int* tile_slot, const void* ybg, const int* cell, long long n, int H, int W,
+                                        int C, const float* a, const float* b, void* yrows, float* out, void* stream);
 int gdmae_tiles_to_dense(const void* Yc, const int* tile_slot, const void* ybg, int B, int H, int W, int C, int elem_bytes,
                          void* out, void* stream);
 /* The reference's dense spatial_features (spt_backbone_mae.py:130-138) from the tile-compact bf16 conv output in one pass:
@@ -540,6 +548,10 @@ int gdmae_spconv_stats(const void* X, int x_f32, const int* nbr, const void* pac
  *   with gdmae_spconv over the same rulebook for the input gradient this replaces the taps + two library GEMMs per stage. */
 int gdmae_decoder_dy(const void* Yc, const int* tile_list, int n_act, const float* k0, const float* k1, const float* rows,
                      const int* cell2pillar, int H, int W, int C, void* dYc, void* stream);
+/* gdmae_decoder_dy with the pillar rows formed in the launch: rows[p] = a2 * (a2 * y + b2 > 0 ? dout[p] : 0) from dout (M, C) fp32, the
+ * gradient of the BatchNorm + ReLU'd pillar rows, and y = the conv output at the site (what gdmae_rows_bwd with c0 = c1 = 0 writes). */
+int gdmae_decoder_dy_rows(const void* Yc, const int* tile_list, int n_act, const float* k0, const float* k1, const float* dout,
+                          const float* a2, const float* b2, const int* cell2pillar, int H, int W, int C, void* dYc, void* stream);
 int gdmae_decoder_site_rulebook(const int* site, const int* n_dev, int sites_per_tok, long long cap_sites, const int* tile_slot,
                                 int H, int W, int* nbr, void* stream);
 long long gdmae_tap_dw_rows(long long n, int M, int N);      /* n_pad: rows G must be allocated for */
@@ -765,6 +777,11 @@ int gdmae_group_gt_points(const float* points, int n_cols, const int* pillar_pt_
                           float* gt_points, int* gt_index, void* stream);
 int gdmae_chamfer(const float* pred, const float* gt, const float* weights, int M, int P1, int P2, float* term,
                   float* dpred, void* stream);
+/* gdmae_group_gt_points (K = P2) followed by gdmae_chamfer (P1 = 16 only) as one launch, the same bits: lane j of a pillar's wavefront
+ * takes target j from the points itself, the (M, P2, 3) targets are never written and the points of a zero-weight pillar are not read. */
+int gdmae_chamfer_points(const float* pred, const float* points, int n_cols, const int* pillar_pt_off, const int* pillar_pts,
+                         const long long* voxel_coords, const float* lo, const float* vs, const float* weights, int M, int P1, int P2,
+                         float* term, float* dpred, void* stream);
 
 /* ---- f2 (next row): on-GPU input pipeline ------------------------------------------------------- *
  * World flip / rotation / scaling (data_augmentor.py:54-143, common_utils.py:99-121), xy range mask
