@@ -20,6 +20,9 @@
 //     sites: 4 accumulators, 1 weight fragment + 4 site fragments per 4 MFMAs.
 //   * epilogue: accumulators -> bf16 -> LDS (site-major) -> 16-byte coalesced stores of the tile rows; the same pass
 //     accumulates per-channel sum / sum of squares of the ROUNDED values over the tile's in-map sites.
+//   * leading-phase skip (round 15): a workgroup whose two halo patches hold nothing but in-map background of the first `lead` stages
+//     starts from the accumulator column those phases leave (ct_pre_block, once per step) and runs the phases lead ..; the tiles are
+//     paired in class order (k_ct_tile_order).  Bit-identical to the full chain; null class / order / pre pointers are the full chain.
 #include "conv_tiles.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -95,29 +98,99 @@ struct CtMaps {
   int k;
 };
 
-// one wavefront per tile: is any in-map site of the 10x10 halo patch covered by a token of any source stage?
+// one wavefront per tile: is any in-map site of the 10x10 halo patch covered by a token of any source stage?  flag[t] = that bit
+// + 2 * the tile's class: the number of LEADING source stages without a token anywhere in the halo patch (every site of theirs holds
+// the stage's background row), capped at k - 1, and 0 for a tile whose halo leaves the map (its zero entries are no background).
 __global__ __launch_bounds__(256) void k_ct_tile_flags(CtMaps Mp, int B, int H, int W, int TH, int TW, int* __restrict__ flag) {
   const int lane = threadIdx.x & 63;
   const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (t >= B * TH * TW) return;
   const int tx = t % TW, r = t / TW, ty = r % TH, b = r / TH;
-  bool act = false;
+  int tok = 0;            // bit g: a token of stage g
+  bool outside = false;
   for (int e = lane; e < 100; e += 64) {
     const int y = ty * 8 - 1 + e / 10, x = tx * 8 - 1 + e % 10;
-    if (y < 0 || y >= H || x < 0 || x >= W) continue;
+    if (y < 0 || y >= H || x < 0 || x >= W) {
+      outside = true;
+      continue;
+    }
     for (int g = 0; g < Mp.k; ++g) {
       const int ls = Mp.ls[g];
-      act |= Mp.map[g][(b * (H >> ls) + (y >> ls)) * (W >> ls) + (x >> ls)] >= 0;
+      tok |= (Mp.map[g][(b * (H >> ls) + (y >> ls)) * (W >> ls) + (x >> ls)] >= 0) << g;
     }
   }
-  const unsigned long long m = __ballot(act);
-  if (lane == 0) flag[t] = m != 0ull;
+  int any = 0;
+  for (int g = 0; g < Mp.k; ++g) any |= (__ballot((tok >> g) & 1) != 0ull) << g;
+  const bool out = __ballot(outside) != 0ull;
+  int cls = 0;
+  while (cls < Mp.k - 1 && !((any >> cls) & 1)) ++cls;
+  if (lane == 0) flag[t] = (any != 0) | ((out ? 0 : cls) << 1);
 }
 
 struct CtFlagLoad {
   const int* flag;
-  __device__ int operator()(long long i) const { return flag[i]; }
+  __device__ int operator()(long long i) const { return flag[i] & 1; }
 };
+
+// Class of every active slot and the slots in stable order of ascending class (a counting sort by ONE workgroup: n_act is some 12 k).
+// tile_order[2 w], tile_order[2 w + 1] are the slots of workgroup w of k_conv3x3_tiles: class 0, the three-phase tiles, first.
+#define CT_ORD_THREADS 1024
+__global__ __launch_bounds__(CT_ORD_THREADS) void k_ct_tile_order(const int* __restrict__ flag, const int* __restrict__ tile_list,
+                                                                  const int* __restrict__ n_act, int* __restrict__ tile_class,
+                                                                  int* __restrict__ tile_order) {
+  __shared__ int wcnt[CT_ORD_THREADS / 64][CT_MAX_SRC];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int n = *n_act;
+  // ---- classes, and how many slots each has
+  int c[CT_MAX_SRC];
+#pragma unroll
+  for (int g = 0; g < CT_MAX_SRC; ++g) c[g] = 0;
+  for (int s = tid; s < n; s += CT_ORD_THREADS) {
+    const int cls = flag[tile_list[s]] >> 1;
+    tile_class[s] = cls;
+#pragma unroll
+    for (int g = 0; g < CT_MAX_SRC; ++g) c[g] += cls == g;
+  }
+#pragma unroll
+  for (int g = 0; g < CT_MAX_SRC; ++g) {
+    for (int o = 32; o > 0; o >>= 1) c[g] += __shfl_xor(c[g], o, 64);
+    if (lane == 0) wcnt[wv][g] = c[g];
+  }
+  __syncthreads();
+  int run[CT_MAX_SRC];    // next free place of each class
+  {
+    int tot[CT_MAX_SRC];
+#pragma unroll
+    for (int g = 0; g < CT_MAX_SRC; ++g) {
+      tot[g] = 0;
+      for (int w = 0; w < CT_ORD_THREADS / 64; ++w) tot[g] += wcnt[w][g];
+    }
+    run[0] = 0;
+#pragma unroll
+    for (int g = 1; g < CT_MAX_SRC; ++g) run[g] = run[g - 1] + tot[g - 1];
+  }
+  __syncthreads();
+  // ---- 1024 consecutive slots at a time: place = class base + slots of the class before this one
+  for (int s0 = 0; s0 < n; s0 += CT_ORD_THREADS) {
+    const int s = s0 + tid;
+    const int cls = s < n ? flag[tile_list[s]] >> 1 : -1;
+    int rank = 0;
+#pragma unroll
+    for (int g = 0; g < CT_MAX_SRC; ++g) {
+      const unsigned long long m = __ballot(cls == g);
+      if (cls == g) rank = __popcll(m & ((1ull << lane) - 1ull));
+      if (lane == 0) wcnt[wv][g] = __popcll(m);
+    }
+    __syncthreads();
+    int before = 0;
+    for (int w = 0; w < wv; ++w) before += cls >= 0 ? wcnt[w][cls] : 0;
+    if (cls >= 0) tile_order[run[cls] + before + rank] = s;
+#pragma unroll
+    for (int g = 0; g < CT_MAX_SRC; ++g)
+      for (int w = 0; w < CT_ORD_THREADS / 64; ++w) run[g] += wcnt[w][g];
+    __syncthreads();
+  }
+}
 struct CtSlotStore {
   int* slot;
   int* list;
@@ -134,8 +207,8 @@ extern "C" size_t gdmae_decoder_tiles_workspace_bytes(int B, int H, int W) {
 
 // maps / strides: HOST arrays of k device pointers / ints (stride of stage g = H / its map's Y, a power of two).
 // tile_slot (B*TH*TW), tile_list (capacity B*TH*TW, ascending tile ids), n_act: device int.
-extern "C" int gdmae_decoder_tiles(const int* const* maps, const int* strides, int k, int B, int H, int W, int* tile_slot,
-                                   int* tile_list, int* n_act, void* workspace, void* stream) {
+static int ct_decoder_tiles(const int* const* maps, const int* strides, int k, int B, int H, int W, int* tile_slot, int* tile_list,
+                            int* tile_class, int* tile_order, int* n_act, void* workspace, void* stream) {
   GD_REQUIRE(k >= 1 && k <= CT_MAX_SRC, "decoder_tiles: 1..3 source stages");
   GD_REQUIRE(H >= 2 && W >= 2 && B >= 1, "decoder_tiles: map too small");
   hipStream_t st = (hipStream_t)stream;
@@ -155,14 +228,33 @@ extern "C" int gdmae_decoder_tiles(const int* const* maps, const int* strides, i
   int* scan_ws = A.take<int>(gd_scan_ws_elems(nt) + 2);
   hipLaunchKernelGGL(k_ct_tile_flags, dim3(gd_div_up(nt, 4)), dim3(256), 0, st, Mp, B, H, W, TH, TW, flag);
   GD_LAUNCH_CHECK();
-  return gd_device_scan<int>(nt, CtFlagLoad{flag}, CtSlotStore{tile_slot, tile_list}, n_act, scan_ws, st);
+  if (int rc = gd_device_scan<int>(nt, CtFlagLoad{flag}, CtSlotStore{tile_slot, tile_list}, n_act, scan_ws, st)) return rc;
+  if (tile_class) {
+    hipLaunchKernelGGL(k_ct_tile_order, dim3(1), dim3(CT_ORD_THREADS), 0, st, (const int*)flag, (const int*)tile_list, (const int*)n_act,
+                       tile_class, tile_order);
+    GD_LAUNCH_CHECK();
+  }
+  return 0;
+}
+
+extern "C" int gdmae_decoder_tiles(const int* const* maps, const int* strides, int k, int B, int H, int W, int* tile_slot,
+                                   int* tile_list, int* n_act, void* workspace, void* stream) {
+  return ct_decoder_tiles(maps, strides, k, B, H, W, tile_slot, tile_list, nullptr, nullptr, n_act, workspace, stream);
+}
+
+// ... and per active slot tile_class (the leading source stages that are background over the tile's whole halo patch, 0 .. k - 1; 0
+// where the halo leaves the map) and tile_order, the slots in stable order of ascending class; both capacity-sized like tile_list.
+extern "C" int gdmae_decoder_tiles_classes(const int* const* maps, const int* strides, int k, int B, int H, int W, int* tile_slot,
+                                           int* tile_list, int* tile_class, int* tile_order, int* n_act, void* workspace, void* stream) {
+  GD_REQUIRE(tile_class != nullptr && tile_order != nullptr, "decoder_tiles_classes: tile_class and tile_order");
+  return ct_decoder_tiles(maps, strides, k, B, H, W, tile_slot, tile_list, tile_class, tile_order, n_act, workspace, stream);
 }
 
 // The same with the single-launch scan (geometry plan, plan.hip): flag (nt ints) + a ZEROED look-back state of
-// gd_decoder_tiles_lb_state_bytes(nt) bytes; two launches.
+// gd_decoder_tiles_lb_state_bytes(nt) bytes; two launches, and a third for tile_class / tile_order (both or neither).
 size_t gd_decoder_tiles_lb_state_bytes(long long nt) { return gd_scan_lb_state_bytes<int>(nt); }
-int gd_decoder_tiles_lb(const int* const* maps, const int* strides, int k, int B, int H, int W, int* tile_slot, int* tile_list, int* n_act,
-                        int* flag, void* lb_state, hipStream_t st) {
+int gd_decoder_tiles_lb(const int* const* maps, const int* strides, int k, int B, int H, int W, int* tile_slot, int* tile_list,
+                        int* tile_class, int* tile_order, int* n_act, int* flag, void* lb_state, hipStream_t st) {
   GD_REQUIRE(k >= 1 && k <= CT_MAX_SRC, "decoder_tiles: 1..3 source stages");
   CtMaps Mp;
   Mp.k = k;
@@ -176,7 +268,13 @@ int gd_decoder_tiles_lb(const int* const* maps, const int* strides, int k, int B
   const long long nt = (long long)B * TH * TW;
   hipLaunchKernelGGL(k_ct_tile_flags, dim3(gd_div_up(nt, 4)), dim3(256), 0, st, Mp, B, H, W, TH, TW, flag);
   GD_LAUNCH_CHECK();
-  return gd_device_scan_lb<int>(nt, CtFlagLoad{flag}, CtSlotStore{tile_slot, tile_list}, GdNoTotal{}, n_act, lb_state, st);
+  if (int rc = gd_device_scan_lb<int>(nt, CtFlagLoad{flag}, CtSlotStore{tile_slot, tile_list}, GdNoTotal{}, n_act, lb_state, st)) return rc;
+  if (tile_class && tile_order) {
+    hipLaunchKernelGGL(k_ct_tile_order, dim3(1), dim3(CT_ORD_THREADS), 0, st, (const int*)flag, (const int*)tile_list, (const int*)n_act,
+                       tile_class, tile_order);
+    GD_LAUNCH_CHECK();
+  }
+  return 0;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -206,13 +304,83 @@ struct CtBPtrs {
   const float* b[CT_MAX_SRC];
 };
 
+#define CT_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_f16((a), (b), (c), 0, 0, 0)
+// byte offset of k-step st of a phase (tap st / CT_KS, 16-channel step st % CT_KS) inside the LDS patch
+#define CT_OFF(st) ((((st) / CT_KS) / 3) * CT_ROW_PITCH + (((st) / CT_KS) % 3) * CT_PSITE + ((st) % CT_KS) * 32)
+// the same k-step in the packed image of a stage (8 k-steps per tap)
+#define CT_WSTEP(st, hf) ((((st) / CT_KS) * 8 + (hf) * CT_KS + ((st) % CT_KS)) * 256)
+// the leading-phase skip is written for the default build only (one phase per stage, four wavefronts)
+#define CT_SKIP_OK (CT_CH == 128 && CT_TPW == 2)
+
+// Pre-accumulators: pre[j][c] = what every site column of k_conv3x3_tiles' accumulators holds in output channel c after phases 0 .. j
+// of a tile whose whole halo patch is in-map background of those stages - the kernel's own chain from a zero accumulator: the 72 MFMAs
+// of each phase in CT_WSTEP order, A = the fragments of Wp, B = the background fragment built like the gather's bgq.  An MFMA result
+// element depends on its A row, its B column and its C element alone, so a tile that starts from pre[j] and runs the phases j + 1 ..
+// holds the bits it would hold after all of them.  Four workgroups of one working wavefront each (a CU's path from L2 to itself);
+// wavefront w = output channels [32 w, 32 w + 32), column 0 is stored.
+// The chain is 72 (k - 1) dependent MFMAs (~4 us) behind 1 KB of weights per step and wavefront: CT_PRE_RING fragments are kept in
+// flight (one at a time the launch took 19.8 us on the training stream).  The stages of Wp are contiguous, so step s of the chain is
+// at s * 256 and the ring runs across the stage boundary; with k = 2 it also requests stage 1's fragments, which exist and are not used.
+#if CT_SKIP_OK
+#define CT_PRE_RING 36
+__device__ __forceinline__ void ct_pre_block(const uint4* __restrict__ Wp, const CtBPtrs& Bp, int k, float* __restrict__ pre, int wv) {
+  if (threadIdx.x >= 64) return;
+  const int lane = threadIdx.x;
+  const uint4* __restrict__ wp = Wp + wv * 64 + lane;
+  CtFrag wr[CT_PRE_RING];
+#pragma unroll
+  for (int s = 0; s < CT_PRE_RING; ++s) wr[s].q = wp[(s / CT_NSTEP) * CT_NSTEP * 256 + CT_WSTEP(s % CT_NSTEP, 0)];
+  CtFrag bg[CT_MAX_SRC - 1][CT_KS];
+#pragma unroll
+  for (int g = 0; g < CT_MAX_SRC - 1; ++g)
+#pragma unroll
+    for (int ks = 0; ks < CT_KS; ++ks) {
+      bg[g][ks].q = make_uint4(0u, 0u, 0u, 0u);
+      if (g + 1 < k) {
+        const float* b = Bp.b[g] + ks * 16 + (lane >> 5) * 8;
+        const float4 b0 = *(const float4*)b, b1 = *(const float4*)(b + 4);
+        bg[g][ks].q.x = gd_pack_f16_relu(b0.x, b0.y); bg[g][ks].q.y = gd_pack_f16_relu(b0.z, b0.w);
+        bg[g][ks].q.z = gd_pack_f16_relu(b1.x, b1.y); bg[g][ks].q.w = gd_pack_f16_relu(b1.z, b1.w);
+      }
+    }
+  f32x16 acc;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+#pragma unroll
+  for (int g = 0; g < CT_MAX_SRC - 1; ++g) {
+    if (g + 1 >= k) break;
+#pragma unroll
+    for (int st = 0; st < CT_NSTEP; ++st) {
+      const int s = g * CT_NSTEP + st, sn = s + CT_PRE_RING;
+      CtFrag a;
+      a.q = wr[s % CT_PRE_RING].q;
+      if (sn < (CT_MAX_SRC - 1) * CT_NSTEP) wr[s % CT_PRE_RING].q = wp[(sn / CT_NSTEP) * CT_NSTEP * 256 + CT_WSTEP(sn % CT_NSTEP, 0)];
+      acc = CT_MFMA(a.h, bg[g][st % CT_KS].h, acc);
+    }
+    if ((lane & 31) == 0) {
+#pragma unroll
+      for (int i = 0; i < 16; ++i) pre[g * CT_C + wv * 32 + 4 * (lane >> 5) + 8 * (i >> 2) + (i & 3)] = acc[i];
+    }
+  }
+}
+#endif
+
 // one workgroup per output channel o: t[k] = sum_c f16(W[o][c][k]) * bg[c] with bg[c] = f16(relu(b[c])) - the operands the tile kernel
 // multiplies -, then the 9 border-class constants ybg[cls][o] = bf16(sum of t[k] over the taps of the class that fall inside the map).
 // Block 0 also writes the background row bgz (Cin) bf16 (what the backward subtracts from its bf16 operand rows).
+// The four workgroups past the C2 channels (launched when pre != NULL) compute the pre-accumulators from Wp, which the launch before
+// this one wrote: they run beside the others instead of as a launch of their own on the training stream.
 __global__ __launch_bounds__(256) void k_ct_class_consts(const float* __restrict__ w, CtBPtrs Bp, int Cin, int C2,
-                                                         unsigned short* __restrict__ bgz, unsigned short* __restrict__ ybg) {
+                                                         unsigned short* __restrict__ bgz, unsigned short* __restrict__ ybg,
+                                                         const uint4* __restrict__ Wp, int k, float* __restrict__ pre) {
   __shared__ double sh[9][256];
   const int o = blockIdx.x;
+  if (o >= C2) {
+#if CT_SKIP_OK
+    ct_pre_block(Wp, Bp, k, pre, o - C2);
+#endif
+    return;
+  }
   double t[9];
 #pragma unroll
   for (int k = 0; k < 9; ++k) t[k] = 0.0;
@@ -248,10 +416,8 @@ __global__ __launch_bounds__(256) void k_ct_class_consts(const float* __restrict
 
 extern "C" size_t gdmae_conv3x3_tiles_packed_bytes(int k) { return (size_t)k * 72 * 4 * 64 * 16; }
 
-// conv_w (C2 = 128, Cin = 128 k, 3, 3) fp32; b: HOST array of k device pointers to the folded BatchNorm shifts (128 each).
-// Wp: gdmae_conv3x3_tiles_packed_bytes(k); bgz (Cin) bf16; ybg (9, 128) bf16.
-extern "C" int gdmae_conv3x3_tiles_pack(const float* conv_w, int C2, int Cin, const float* const* b, int k, void* Wp, void* bgz,
-                                        void* ybg, void* stream) {
+static int ct_pack(const float* conv_w, int C2, int Cin, const float* const* b, int k, void* Wp, void* bgz, void* ybg, float* pre,
+                   void* stream) {
   GD_REQUIRE(C2 == CT_C && k >= 1 && k <= CT_MAX_SRC && Cin == CT_C * k, "conv3x3_tiles: 128 output channels, 128 per source");
   hipStream_t st = (hipStream_t)stream;
   const int nsteps = k * 72;
@@ -259,9 +425,26 @@ extern "C" int gdmae_conv3x3_tiles_pack(const float* conv_w, int C2, int Cin, co
   GD_LAUNCH_CHECK();
   CtBPtrs Bp;
   for (int g = 0; g < CT_MAX_SRC; ++g) Bp.b[g] = g < k ? b[g] : nullptr;
-  hipLaunchKernelGGL(k_ct_class_consts, dim3(C2), dim3(256), 0, st, conv_w, Bp, Cin, C2, (unsigned short*)bgz, (unsigned short*)ybg);
+  const bool with_pre = CT_SKIP_OK && pre != nullptr && k >= 2;      // k = 1: no phase to skip, no row of pre
+  hipLaunchKernelGGL(k_ct_class_consts, dim3(C2 + (with_pre ? 4 : 0)), dim3(256), 0, st, conv_w, Bp, Cin, C2, (unsigned short*)bgz,
+                     (unsigned short*)ybg, (const uint4*)Wp, k, pre);
   GD_LAUNCH_CHECK();
   return 0;
+}
+
+// conv_w (C2 = 128, Cin = 128 k, 3, 3) fp32; b: HOST array of k device pointers to the folded BatchNorm shifts (128 each).
+// Wp: gdmae_conv3x3_tiles_packed_bytes(k); bgz (Cin) bf16; ybg (9, 128) bf16.
+extern "C" int gdmae_conv3x3_tiles_pack(const float* conv_w, int C2, int Cin, const float* const* b, int k, void* Wp, void* bgz,
+                                        void* ybg, void* stream) {
+  return ct_pack(conv_w, C2, Cin, b, k, Wp, bgz, ybg, nullptr, stream);
+}
+
+// ... and pre (k - 1, 128) fp32, the pre-accumulators gdmae_conv3x3_tiles_fwd_skip starts from (nothing is written for k = 1), in the
+// same two launches.
+extern "C" int gdmae_conv3x3_tiles_pack_pre(const float* conv_w, int C2, int Cin, const float* const* b, int k, void* Wp, void* bgz,
+                                            void* ybg, float* pre, void* stream) {
+  GD_REQUIRE(pre != nullptr, "conv3x3_tiles_pack_pre: pre");
+  return ct_pack(conv_w, C2, Cin, b, k, Wp, bgz, ybg, pre, stream);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -282,32 +465,42 @@ struct CtArgs {
   int n_act, H, W, TH, TW;
   unsigned short* Yc;        // (n_act * 64, 128) bf16
   float* part;               // (n_act, 2, 128) per-tile sum / sum of squares over the in-map sites
+  // leading-phase skip (all three or none; none = workgroup w takes slots 2 w, 2 w + 1 and runs every phase from zero)
+  const int* tile_class;     // (n_act) leading stages that are background over the slot's whole halo patch
+  const int* tile_order;     // (n_act) slots in ascending class: workgroup w takes tile_order[2 w], tile_order[2 w + 1]
+  const float* pre;          // (k - 1, 128) ct_pre_block
 };
-
-#define CT_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_f16((a), (b), (c), 0, 0, 0)
-
-// byte offset of k-step st of a phase (tap st / CT_KS, 16-channel step st % CT_KS) inside the LDS patch
-#define CT_OFF(st) ((((st) / CT_KS) / 3) * CT_ROW_PITCH + (((st) / CT_KS) % 3) * CT_PSITE + ((st) % CT_KS) * 32)
-// the same k-step in the packed image of a stage (8 k-steps per tap)
-#define CT_WSTEP(st, hf) ((((st) / CT_KS) * 8 + (hf) * CT_KS + ((st) % CT_KS)) * 256)
 
 __global__ __launch_bounds__(CT_THREADS, CT_TPW == 2 ? (CT_CH == 64 ? 3 : 2) : 1) void k_conv3x3_tiles(CtArgs A) {
   extern __shared__ __align__(16) unsigned char lds[];
   const int tid = threadIdx.x, lane = tid & 63, wvg = tid >> 6;
   const int wv = wvg & 3;              // output-channel block of the wavefront
   const int tg = wvg >> 2;             // its pair of tiles
-  const int slot0 = blockIdx.x * CT_TPW;
-  int tb[CT_TPW], ty0[CT_TPW], tx0[CT_TPW];
+  const int pos0 = blockIdx.x * CT_TPW;
+  int slot[CT_TPW], tb[CT_TPW], ty0[CT_TPW], tx0[CT_TPW];
   bool have[CT_TPW];
 #pragma unroll
   for (int t = 0; t < CT_TPW; ++t) {
-    have[t] = slot0 + t < A.n_act;
-    const int tile = have[t] ? A.tile_list[slot0 + t] : 0;
+    have[t] = pos0 + t < A.n_act;
+    slot[t] = have[t] ? (A.tile_order ? A.tile_order[pos0 + t] : pos0 + t) : 0;
+    const int tile = have[t] ? A.tile_list[slot[t]] : 0;
     tx0[t] = (tile % A.TW) * 8;
     const int r = tile / A.TW;
     ty0[t] = (r % A.TH) * 8;
     tb[t] = r / A.TH;
   }
+  // phases 0 .. lead - 1 see nothing but in-map background in BOTH halo patches: the accumulators start from what those phases leave
+  // in every site column (ct_pre_block) and the phases are not run.  Workgroup-uniform; a missing second tile follows the first.
+  int lead = 0;
+#if CT_SKIP_OK
+  if (A.tile_class) {
+    lead = A.tile_class[slot[0]];
+    if (have[1]) {
+      const int l1 = A.tile_class[slot[1]];
+      lead = l1 < lead ? l1 : lead;
+    }
+  }
+#endif
   const int lc = tid % CT_CPS;   // 16-byte chunk (8 channels) of a phase's CT_CH channels of a patch site
   const int lsg = tid / CT_CPS;  // patch entry within a pass
   // site operand: lane n = lane & 31 -> site (row n >> 3 of a 4-row half tile, column n & 7), k-group lane >> 5
@@ -315,8 +508,20 @@ __global__ __launch_bounds__(CT_THREADS, CT_TPW == 2 ? (CT_CH == 64 ? 3 : 2) : 1
   f32x16 acc0, acc1, acc2, acc3;
 #pragma unroll
   for (int i = 0; i < 16; ++i) acc0[i] = acc1[i] = acc2[i] = acc3[i] = 0.f;
+#if CT_SKIP_OK
+  if (lead > 0) {
+    // register 4 j + i of a lane = output channel 32 wv + 8 j + 4 (lane >> 5) + i (the layout the epilogue reads), the same in all columns
+    const float* pr = A.pre + (lead - 1) * CT_C + wv * 32 + 4 * (lane >> 5);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float4 v = *(const float4*)(pr + 8 * j);
+      acc0[4 * j] = v.x; acc0[4 * j + 1] = v.y; acc0[4 * j + 2] = v.z; acc0[4 * j + 3] = v.w;
+    }
+    acc1 = acc2 = acc3 = acc0;
+  }
+#endif
 
-  for (int g = 0; g < A.k; ++g) {
+  for (int g = lead; g < A.k; ++g) {
     const CtSrc S = A.src[g];
     const int ls = S.ls, sm = (1 << ls) - 1;
     const int Hs = A.H >> ls, Ws = A.W >> ls;
@@ -464,7 +669,7 @@ __global__ __launch_bounds__(CT_THREADS, CT_TPW == 2 ? (CT_CH == 64 ? 3 : 2) : 1
     for (int p = 0; p < 64 / CT_ESPP; ++p) {
       const int site = p * CT_ESPP + elsg;
       const uint4 v = *(const uint4*)(lds + t * CT_STAGE_PITCH + site * CT_SITE_PITCH + elc * 16);
-      *(uint4*)(A.Yc + ((long long)(slot0 + t) * GD_TILE_SITES + site) * CT_C + elc * 8) = v;
+      *(uint4*)(A.Yc + ((long long)slot[t] * GD_TILE_SITES + site) * CT_C + elc * 8) = v;
       if (ty0[t] + (site >> 3) < A.H && tx0[t] + (site & 7) < A.W) {
         float f[8];
         ct_unpack8(v, f);
@@ -498,7 +703,7 @@ __global__ __launch_bounds__(CT_THREADS, CT_TPW == 2 ? (CT_CH == 64 ? 3 : 2) : 1
     float v = 0.f;
 #pragma unroll
     for (int w = 0; w < CT_NWAVES; ++w) v += red[((t * CT_NWAVES + w) * 2 + stat) * CT_C + ch];
-    A.part[(long long)(slot0 + t) * 256 + tid] = v;
+    A.part[(long long)slot[t] * 256 + tid] = v;
   }
 }
 
@@ -593,11 +798,11 @@ extern "C" size_t gdmae_conv3x3_tiles_workspace_bytes(int n_act) {
 // P / map / a / b / strides: HOST arrays over the k source stages (device pointers).  Yc (n_act * 64, 128) bf16 out.
 // BatchNorm2d (training) of the conv output over all B*H*W sites: stats f64[256] = mean | rstd, ab f32[256] = folded
 // scale | shift, mv f32[256] = mean | biased variance; running statistics updated when running_mean != NULL.
-extern "C" int gdmae_conv3x3_tiles_fwd(const void* const* P, const int* const* maps, const float* const* a, const float* const* b,
-                                       const int* strides, int k, const void* Wp, const void* ybg, const int* tile_list, int n_act,
-                                       int B, int H, int W, void* Yc, const float* gamma, const float* beta, double eps,
-                                       double momentum, float* running_mean, float* running_var, long long* num_batches,
-                                       double* stats, float* ab, float* mv, void* workspace, void* stream) {
+static int ct_fwd(const void* const* P, const int* const* maps, const float* const* a, const float* const* b, const int* strides, int k,
+                  const void* Wp, const void* ybg, const int* tile_list, int n_act, int B, int H, int W, void* Yc, const float* gamma,
+                  const float* beta, double eps, double momentum, float* running_mean, float* running_var, long long* num_batches,
+                  double* stats, float* ab, float* mv, const int* tile_class, const int* tile_order, const float* pre, void* workspace,
+                  void* stream) {
   GD_REQUIRE(k >= 1 && k <= CT_MAX_SRC, "conv3x3_tiles: 1..3 source stages");
   GD_REQUIRE(H >= 2 && W >= 2, "conv3x3_tiles: map too small");
   hipStream_t st = (hipStream_t)stream;
@@ -621,6 +826,9 @@ extern "C" int gdmae_conv3x3_tiles_fwd(const void* const* P, const int* const* m
   A.n_act = n_act;
   A.H = H; A.W = W; A.TH = (H + 7) / 8; A.TW = (W + 7) / 8;
   A.Yc = (unsigned short*)Yc;
+  A.tile_class = CT_SKIP_OK ? tile_class : nullptr;
+  A.tile_order = CT_SKIP_OK ? tile_order : nullptr;
+  A.pre = CT_SKIP_OK ? pre : nullptr;
   GdArena ar(workspace, gdmae_conv3x3_tiles_workspace_bytes(n_act));
   float* part = ar.take<float>((size_t)(n_act > 0 ? n_act : 1) * 256);
   float* red = ar.take<float>((size_t)(CT_NRED + 2) * 256);
@@ -639,6 +847,30 @@ extern "C" int gdmae_conv3x3_tiles_fwd(const void* const* P, const int* const* m
   GD_LAUNCH_CHECK();
   return gd_bn_fold_from_partials(st, red, CT_NRED + 2, CT_C, (double)B * H * W, gamma, beta, eps, momentum, running_mean,
                                   running_var, num_batches, stats, ab, mv);
+}
+
+extern "C" int gdmae_conv3x3_tiles_fwd(const void* const* P, const int* const* maps, const float* const* a, const float* const* b,
+                                       const int* strides, int k, const void* Wp, const void* ybg, const int* tile_list, int n_act,
+                                       int B, int H, int W, void* Yc, const float* gamma, const float* beta, double eps,
+                                       double momentum, float* running_mean, float* running_var, long long* num_batches,
+                                       double* stats, float* ab, float* mv, void* workspace, void* stream) {
+  return ct_fwd(P, maps, a, b, strides, k, Wp, ybg, tile_list, n_act, B, H, W, Yc, gamma, beta, eps, momentum, running_mean, running_var,
+                num_batches, stats, ab, mv, nullptr, nullptr, nullptr, workspace, stream);
+}
+
+// The same results bit for bit without the leading phases that only see background: tile_class / tile_order of
+// gdmae_decoder_tiles_classes (or the geometry plan) and pre of gdmae_conv3x3_tiles_pack_pre with this Wp.  Workgroups take their two
+// slots from tile_order; Yc and the statistics partials stay indexed by slot.  All three NULL: gdmae_conv3x3_tiles_fwd.
+extern "C" int gdmae_conv3x3_tiles_fwd_skip(const void* const* P, const int* const* maps, const float* const* a, const float* const* b,
+                                            const int* strides, int k, const void* Wp, const void* ybg, const int* tile_list, int n_act,
+                                            int B, int H, int W, void* Yc, const float* gamma, const float* beta, double eps,
+                                            double momentum, float* running_mean, float* running_var, long long* num_batches,
+                                            double* stats, float* ab, float* mv, const int* tile_class, const int* tile_order,
+                                            const float* pre, void* workspace, void* stream) {
+  const bool none = !tile_class && !tile_order && !pre;
+  GD_REQUIRE(none || (tile_class && tile_order && (pre || k < 2)), "conv3x3_tiles_fwd_skip: tile_class, tile_order and pre, or none of them");
+  return ct_fwd(P, maps, a, b, strides, k, Wp, ybg, tile_list, n_act, B, H, W, Yc, gamma, beta, eps, momentum, running_mean, running_var,
+                num_batches, stats, ab, mv, tile_class, tile_order, pre, workspace, stream);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -61,7 +61,8 @@ struct GdWinStage {
 };
 int gd_plan_windows_all(const GdWinStage* stages, int n_stages, hipStream_t st);
 size_t gd_decoder_tiles_lb_state_bytes(long long nt);
-int gd_decoder_tiles_lb(const int* const* maps, const int* strides, int k, int B, int H, int W, int* tile_slot, int* tile_list, int* n_act,
+int gd_decoder_tiles_lb(const int* const* maps, const int* strides, int k, int B, int H, int W, int* tile_slot, int* tile_list,
+                        int* tile_class, int* tile_order, int* n_act,
                         int* flag, void* lb_state, hipStream_t st);
 int gd_decoder_site_rulebook(const int* site, const int* n_dev, int sites_per_tok, long long cap_sites, const int* tile_slot, int H, int W,
                              int* nbr, hipStream_t st);
@@ -108,7 +109,7 @@ struct Offsets {
     long long tok_cell, map, nbr_subm, nbr_subm_t, nbr_down, nbr_down_t, up_sites, win_ws;
     long long w[2][7];
   } s[GDMAE_PLAN_MAX_STAGES];
-  long long dec_slot, dec_list, dec_flag, dec_nbr[3];
+  long long dec_slot, dec_list, dec_flag, dec_class, dec_order, dec_nbr[3];
   size_t lb_bytes, vox_ws_bytes;
   int n_counts;
   bool dec;
@@ -309,11 +310,14 @@ int layout(const gdmae_plan_params* p, gdmae_plan_buffer* table, int max_entries
         O.s[i].w[sh][k] = L.add(nm, sizeof(int) * (k < 5 ? g.cap : wcap));
       }
   }
-  O.dec_slot = O.dec_list = O.dec_flag = -1;
+  O.dec_slot = O.dec_list = O.dec_flag = O.dec_class = O.dec_order = -1;
   if (O.dec) {
     O.dec_slot = L.add("dec.tile_slot", sizeof(int) * nt);
     O.dec_list = L.add("dec.tile_list", sizeof(int) * nt);
     O.dec_flag = L.add("dec.flag", sizeof(int) * nt);
+    // leading all-background stages of every active slot, and the slots in ascending order of that class (k_conv3x3_tiles' pairing)
+    O.dec_class = L.add("dec.tile_class", sizeof(int) * nt);
+    O.dec_order = L.add("dec.tile_order", sizeof(int) * nt);
     // rulebooks of the conv_out backward: tile-compact row of every (active site, tap) per source stage
     for (int g = 0; g < p->n_dec; ++g) {
       const StageGeo& sg = O.geo[p->dec_sources[g]];
@@ -452,7 +456,8 @@ extern "C" int gdmae_geometry_plan(const gdmae_plan_params* p, const float* poin
       maps[g] = I(O.s[p->dec_sources[g]].map);
       ups[g] = O.geo[p->dec_sources[g]].up_s;
     }
-    int rc = gd_decoder_tiles_lb(maps, ups, p->n_dec, B, gy, gx, I(O.dec_slot), I(O.dec_list), n_act, I(O.dec_flag), lb, st);
+    int rc = gd_decoder_tiles_lb(maps, ups, p->n_dec, B, gy, gx, I(O.dec_slot), I(O.dec_list), I(O.dec_class), I(O.dec_order), n_act,
+                                 I(O.dec_flag), lb, st);
     if (rc) return rc;
     for (int g = 0; g < p->n_dec; ++g) {
       const int si = p->dec_sources[g];

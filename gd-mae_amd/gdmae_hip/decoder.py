@@ -62,6 +62,10 @@ BLOCK_BWD = os.environ.get("GDMAE_DEC_BLOCK", "1")
 DY_ROWS = os.environ.get("GDMAE_DEC_DY_ROWS", "1") != "0"
 # "1" = the tile path gathers the pillar rows and writes their BatchNorm + ReLU in one launch; "0" = gather, then a second pass over the rows
 GATHER_FUSED = os.environ.get("GDMAE_DEC_GATHER_FUSED", "1") != "0"
+# tile convolution: "1" = leading source stages that are background over a tile's whole halo patch are not multiplied (the accumulators
+# start from the pre-accumulators of gdmae_conv3x3_tiles_pack_pre, workgroups pair the tiles in class order; the same bits), "0" = every
+# tile runs every phase from zero in ascending pairs (A/B runs), "ascending" = the skip on ascending pairs (what the pairing order is worth)
+CT_SKIP = os.environ.get("GDMAE_CT_SKIP", "1")
 
 
 # sparse_decoder(..., pre_conv_hook=callable): invoked once right before the decoder's tile convolution is launched (the one
@@ -136,6 +140,7 @@ class TileConv:
     tiles: gplan.DecoderTiles
     maps: list
     ups: list
+    skip: str = "0"           # CT_SKIP as the caller read it: "0", "1" or "ascending"
 
 
 @dataclass(frozen=True, eq=False)
@@ -173,8 +178,17 @@ def _forward_tiles(geom, pre_conv_hook, conv_w, gamma2, beta2, pillar_cell, Ps, 
     bgz = torch.empty(Cin, dtype=cdt, device=dev)
     ybg = torch.empty(9, C2, dtype=cdt, device=dev)
     a_l, b_l = [ab[:w] for ab, w in zip(ab_l, widths)], [ab[w:] for ab, w in zip(ab_l, widths)]
-    L.call("gdmae_conv3x3_tiles_pack", L.ptr(conv_w), C2, Cin, L.host_ptrs(b_l), k, L.ptr(Wp), L.ptr(bgz), L.ptr(ybg),
-           L.stream())
+    # the path is the call's (TileConv.skip), and needs a tile set that came with its classes
+    skip = tc.skip != "0" and k >= 2 and dt.tile_class is not None and dt.tile_order is not None
+    pre = order = None
+    if skip:
+        pre = torch.empty(k - 1, C2, dtype=torch.float32, device=dev)
+        L.call("gdmae_conv3x3_tiles_pack_pre", L.ptr(conv_w), C2, Cin, L.host_ptrs(b_l), k, L.ptr(Wp), L.ptr(bgz), L.ptr(ybg), L.ptr(pre),
+               L.stream())
+        order = dt.tile_order if tc.skip != "ascending" else torch.arange(dt.n_act, dtype=torch.int32, device=dev)
+    else:
+        L.call("gdmae_conv3x3_tiles_pack", L.ptr(conv_w), C2, Cin, L.host_ptrs(b_l), k, L.ptr(Wp), L.ptr(bgz), L.ptr(ybg),
+               L.stream())
     y2 = torch.empty(max(dt.n_act, 1) * 64, C2, dtype=cdt, device=dev)
     stats2 = torch.empty(2 * C2, dtype=torch.float64, device=dev)
     ab2 = torch.empty(2 * C2, dtype=torch.float32, device=dev)
@@ -186,10 +200,10 @@ def _forward_tiles(geom, pre_conv_hook, conv_w, gamma2, beta2, pillar_cell, Ps, 
         pre_conv_hook()
     with timing.kernel("k_conv3x3_tiles", dt.n_act * 64 * (Cin + C2) * 2, flops,
                        {"dense_equivalent_TFLOPs_per_launch": round(2.0 * B * H * W * C2 * 9 * Cin / 1e12, 4), "active_tiles": dt.n_act}):
-        L.call("gdmae_conv3x3_tiles_fwd", L.host_ptrs([P.contiguous() for P in Ps]), L.host_ptrs(tc.maps), L.host_ptrs(a_l),
+        L.call("gdmae_conv3x3_tiles_fwd_skip", L.host_ptrs([P.contiguous() for P in Ps]), L.host_ptrs(tc.maps), L.host_ptrs(a_l),
                L.host_ptrs(b_l), L.host_i32(tc.ups), k, L.ptr(Wp), L.ptr(ybg), L.ptr(dt.tile_list), dt.n_act, B, H, W,
                L.ptr(y2), L.ptr(gamma2), L.ptr(beta2), float(geom.eps2), mom, L.ptr(rm), L.ptr(rv), L.ptr(nb), L.ptr(stats2),
-               L.ptr(ab2), L.ptr(mv2), L.ptr(ws), L.stream())
+               L.ptr(ab2), L.ptr(mv2), L.ptr(dt.tile_class) if skip else None, L.ptr(order), L.ptr(pre), L.ptr(ws), L.stream())
     M = pillar_cell.numel()
     yrows = torch.empty(M, C2, dtype=cdt, device=dev)
     out = None
@@ -690,7 +704,7 @@ def sparse_decoder(model_cfg, deblocks, conv_out, hidden, pillar_cell, cell2pill
     if cdt == torch.bfloat16 and conv_impl == 'tiles':
         ep = hidden[0]._plan
         tile_conv = TileConv(gplan.decoder_tiles(ep, src_idx, Y, X), [hidden[i].stage_plan.map for i in src_idx],
-                             [Y // hidden[i].stage_plan.Y for i in src_idx])
+                             [Y // hidden[i].stage_plan.Y for i in src_idx], CT_SKIP)
     for i, src in enumerate(model_cfg.FEATURES_SOURCE):
         h = hidden[int(src[-1]) - 1]
         sp = h.stage_plan

@@ -82,6 +82,10 @@ SIGNATURES = {
     "gdmae_conv3x3_tiles_workspace_bytes": (_Z, [_I]),
     "gdmae_conv3x3_tiles_fwd": (_I, [_P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _D, _D, _P, _P, _P, _P, _P, _P,
                                      _P, _P]),
+    "gdmae_decoder_tiles_classes": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "gdmae_conv3x3_tiles_pack_pre": (_I, [_P, _I, _I, _P, _I, _P, _P, _P, _P, _P]),
+    "gdmae_conv3x3_tiles_fwd_skip": (_I, [_P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _D, _D, _P, _P, _P, _P, _P, _P,
+                                          _P, _P, _P, _P, _P]),
     "gdmae_tiles_gather_rows": (_I, [_P, _P, _P, _P, _L, _I, _I, _I, _I, _P, _P]),
     "gdmae_tiles_gather_rows_affine_relu": (_I, [_P, _P, _P, _P, _L, _I, _I, _I, _P, _P, _P, _P, _P]),
     "gdmae_tiles_to_dense": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P]),

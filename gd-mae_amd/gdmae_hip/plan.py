@@ -145,6 +145,9 @@ class DecoderTiles:
     tile_slot: torch.Tensor            # (B * ceil(H/8) * ceil(W/8),) int32 tile -> slot / -1
     tile_list: torch.Tensor            # (n_act,) int32 ascending tile ids
     nbr: Optional[list] = None         # per source stage (n_sites, 9) int32: tile-compact row of (site, tap) / -1 (conv_out backward)
+    # leading-phase skip of the tile convolution (gdmae_conv3x3_tiles_fwd_skip)
+    tile_class: Optional[torch.Tensor] = None   # (n_act,) int32 leading source stages that are background over the slot's whole halo patch
+    tile_order: Optional[torch.Tensor] = None   # (n_act,) int32 slots in stable order of ascending class
 
 
 @dataclass
@@ -192,12 +195,13 @@ def _drop_arrays(drop_info):
 
 
 def _decoder_tiles_launch(maps, ups, B, H, W, dev) -> dict:
-    """Enqueue gdmae_decoder_tiles on the current stream (capacity-sized outputs, count left on the device)."""
+    """Enqueue gdmae_decoder_tiles_classes on the current stream (capacity-sized outputs, count left on the device)."""
     nt = B * ((H + 7) // 8) * ((W + 7) // 8)
-    r = dict(tile_slot=_empty(nt, I32, dev), tile_list=_empty(nt, I32, dev), n_act=_empty(1, I32, dev), B=B, H=H, W=W)
+    r = dict(tile_slot=_empty(nt, I32, dev), tile_list=_empty(nt, I32, dev), tile_class=_empty(nt, I32, dev),
+             tile_order=_empty(nt, I32, dev), n_act=_empty(1, I32, dev), B=B, H=H, W=W)
     ws = _empty(L.load().gdmae_decoder_tiles_workspace_bytes(B, H, W), torch.uint8, dev)
-    L.call("gdmae_decoder_tiles", L.host_ptrs(maps), L.host_i32(ups), len(maps), B, H, W, L.ptr(r["tile_slot"]),
-           L.ptr(r["tile_list"]), L.ptr(r["n_act"]), L.ptr(ws), L.stream())
+    L.call("gdmae_decoder_tiles_classes", L.host_ptrs(maps), L.host_i32(ups), len(maps), B, H, W, L.ptr(r["tile_slot"]),
+           L.ptr(r["tile_list"]), L.ptr(r["tile_class"]), L.ptr(r["tile_order"]), L.ptr(r["n_act"]), L.ptr(ws), L.stream())
     r["_ws"] = ws
     return r
 
@@ -215,7 +219,7 @@ def decoder_tiles(ep: "EncoderPlan", sources, H: int, W: int) -> DecoderTiles:
     assert all(sp.Y * u == H and sp.X * u == W for sp, u in zip(st, ups))
     r = _decoder_tiles_launch([sp.map for sp in st], ups, B, H, W, st[0].map.device)
     n = int(r["n_act"].item())
-    ep.dec_tiles = DecoderTiles(sources, B, H, W, n, r["tile_slot"], r["tile_list"][:n])
+    ep.dec_tiles = DecoderTiles(sources, B, H, W, n, r["tile_slot"], r["tile_list"][:n], None, r["tile_class"][:n], r["tile_order"][:n])
     ep.dec_tiles.nbr = _site_rulebooks(ep.dec_tiles, st, ups)
     return ep.dec_tiles
 
@@ -372,7 +376,8 @@ def _encoder_finalize(e: dict, allc, M: int) -> EncoderPlan:
     dt = None
     if dec is not None:
         n_act = int(allc[ns + 16 * ns])
-        dt = DecoderTiles(dec["sources"], dec["B"], dec["H"], dec["W"], n_act, dec["tile_slot"], dec["tile_list"][:n_act])
+        dt = DecoderTiles(dec["sources"], dec["B"], dec["H"], dec["W"], n_act, dec["tile_slot"], dec["tile_list"][:n_act], None,
+                          dec["tile_class"][:n_act], dec["tile_order"][:n_act])
     return EncoderPlan(e["mask"][:M] if e["masked"] else None, e["tok_pillar"][:stages[0].n_tok], stages, dt)
 
 
@@ -613,7 +618,7 @@ class PlanPrefetch:
             nt = B * ((gy + 7) // 8) * ((gx + 7) // 8)
             nbrs = [V(f"dec.nbr{g}", i32, stages[int(si)].n_tok * geo[int(si)]["up_s"] ** 2, 9) for g, si in enumerate(self.dec_sources)]
             dt = DecoderTiles(tuple(int(i) for i in self.dec_sources), B, gy, gx, n_act, V("dec.tile_slot", i32, nt), V("dec.tile_list", i32, n_act),
-                              nbrs)
+                              nbrs, V("dec.tile_class", i32, n_act), V("dec.tile_order", i32, n_act))
         ep = EncoderPlan(V("mask", f32, M) if self.masked else None, V("tok_pillar", i32, stages[0].n_tok if not geo[0]["strided"] else n_vis),
                          stages, dt)
         if self.masked and A.has("vfe.row_tok"):

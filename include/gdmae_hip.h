@@ -331,6 +331,25 @@ int gdmae_conv3x3_tiles_fwd(const void* const* P, const int* const* maps, const 
                             int H, int W, void* Yc, const float* gamma, const float* beta, double eps, double momentum,
                             float* running_mean, float* running_var, long long* num_batches, double* stats, float* ab,
                             float* mv, void* workspace, void* stream);
+/* Leading-phase skip of the tile convolution: the same Yc / statistics bit for bit, without the products of the leading source stages
+ * that hold nothing but their background row relu(b_g) over a tile's whole 10x10 halo patch.
+ *   gdmae_decoder_tiles_classes  gdmae_decoder_tiles + per active slot tile_class (number of such leading stages, 0 .. k - 1; 0 for a
+ *                                tile whose halo leaves the map) and tile_order (the slots in stable order of ascending class), both
+ *                                with the capacity of tile_list; same workspace
+ *   gdmae_conv3x3_tiles_pack_pre gdmae_conv3x3_tiles_pack + pre (k - 1, 128) fp32: the accumulator column the kernel's own MFMA chain
+ *                                leaves after phases 0 .. j on an all-background patch (four more workgroups of the pack's second launch)
+ *   gdmae_conv3x3_tiles_fwd_skip gdmae_conv3x3_tiles_fwd whose workgroups pair the slots along tile_order and start from pre;
+ *                                tile_class = tile_order = pre = NULL is gdmae_conv3x3_tiles_fwd */
+int gdmae_decoder_tiles_classes(const int* const* maps, const int* strides, int k, int B, int H, int W, int* tile_slot, int* tile_list,
+                                int* tile_class, int* tile_order, int* n_act, void* workspace, void* stream);
+int gdmae_conv3x3_tiles_pack_pre(const float* conv_w, int C2, int Cin, const float* const* b, int k, void* Wp, void* bgz, void* ybg,
+                                 float* pre, void* stream);
+int gdmae_conv3x3_tiles_fwd_skip(const void* const* P, const int* const* maps, const float* const* a, const float* const* b,
+                                 const int* strides, int k, const void* Wp, const void* ybg, const int* tile_list, int n_act, int B,
+                                 int H, int W, void* Yc, const float* gamma, const float* beta, double eps, double momentum,
+                                 float* running_mean, float* running_var, long long* num_batches, double* stats, float* ab,
+                                 float* mv, const int* tile_class, const int* tile_order, const float* pre, void* workspace,
+                                 void* stream);
 int gdmae_tiles_gather_rows(const void* Yc, const int* tile_slot, const void* ybg, const int* cell, long long n, int H, int W,
                             int C, int elem_bytes, void* out, void* stream);
 /* gdmae_tiles_gather_rows of a bf16 map that also writes out[i] = relu(a * yrows[i] + b) in fp32 (C % 8 == 0) */
@@ -850,7 +869,8 @@ int gdmae_group_inner_inds(const long long* inverse_inds, long long n, long long
  * ("points", "point_coords", "inverse", "inverse32", "voxel_coords", "pillar_cell", "pt_off", "pillar_pts", "point_rank",
  * "sample_off", "pillar_mean", "cell2pillar"), "points_pm" / "row_pillar", "mask", "tok_pillar", per stage i "s<i>.tok_cell",
  * "s<i>.map", "s<i>.nbr_subm", "s<i>.nbr_subm_t", "s<i>.nbr_down", "s<i>.nbr_down_t", "s<i>.up_sites", per shift k
- * "s<i>.w<k>.{tok_win,tok_level,tok_slot,tok_pos,csr_tok,win_start,win_len}", "dec.tile_slot" / "dec.tile_list", when masked with
+ * "s<i>.w<k>.{tok_win,tok_level,tok_slot,tok_pos,csr_tok,win_start,win_len}", "dec.tile_slot" / "dec.tile_list" / "dec.tile_class" / "dec.tile_order"
+ * (gdmae_decoder_tiles_classes), when masked with
  * pillar-major rows "vfe.row_tok" (N: token of each pillar-major row's pillar / -1), "vfe.vis_rows" / "vfe.vis_tok" (Nv: the rows of
  * the visible pillars, ascending, and their tokens), "vfe.tok_row_off" (tokens + 1: first of each token's rows among those), and
  * "counts" = int32 [N points kept, M pillars | tokens of stage 0.. | 8 per (stage, shift): windows per level (3), tokens per
