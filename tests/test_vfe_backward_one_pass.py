@@ -26,7 +26,9 @@ CASES = {
     "crowded": [1, 700, 3, 1, 2600, 17, 2, 2, 1, 90, 31, 33, 1],      # a crowded pillar; N = 3 482 is not a multiple of 32
     "tiny": [1] * 300,                                                # 32 pillars per tile
     "one_tile": [5, 1, 9, 2],                                         # N = 17: less than one tile
-    "many_tiles": [40] * 600 + [9000, 1, 7, 9000],                    # 1 313 tiles: more than the grid cap of 1 024, N % 32 = 24
+    # 1 313 tiles, N % 32 = 24.  A workgroup takes four tiles per pass, so this is 329 workgroups - below the grid cap of 1 024: layer 1
+    # (k_vfe1) makes ONE pass; later passes of its tile loop are reached by ``deep`` of tests/test_vfe_point_layer_gpu.py
+    "many_tiles": [40] * 600 + [9000, 1, 7, 9000],
 }
 LO, VS, NX = (0.0, -40.0, -3.0), (0.32, 0.32, 6.0), 64
 
