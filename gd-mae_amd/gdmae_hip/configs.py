@@ -176,6 +176,32 @@ def waymo_finetune_data_cfg():
     return aug, proc
 
 
+def _waymo_late_world_cfg():
+    """The world augmentors gd_mae_iou.yaml and gd_mae_ts.yaml share (they differ from gd_mae.yaml's: flip along y only, full-circle
+    rotation at 0.7, scaling 0.9 - 1.1 at 0.5)."""
+    return [{'NAME': 'random_world_flip', 'PROBABILITY': 0.5, 'ALONG_AXIS_LIST': ['y']},
+            {'NAME': 'random_world_rotation', 'PROBABILITY': 0.7, 'WORLD_ROT_ANGLE': [-3.14159265, 3.14159265]},
+            {'NAME': 'random_world_scaling', 'PROBABILITY': 0.5, 'WORLD_SCALE_RANGE': [0.9, 1.1]}]
+
+
+def waymo_iou_finetune_data_cfg():
+    """(AUG_CONFIG_LIST, DATA_PROCESSOR) of waymo_models/gd_mae_iou.yaml:18-71: gt_sampling (no REMOVE_POINTS key: the sampler's
+    default, True), flip, rotation, scaling, random_world_drop.  Built by ``input_pipeline.finetune_input_pipeline``."""
+    aug, proc = waymo_finetune_data_cfg()
+    sampler = aug[0]
+    del sampler['REMOVE_POINTS']
+    return [sampler] + _waymo_late_world_cfg() + [{'NAME': 'random_world_drop', 'PROBABILITY': 0.5, 'DROP_RATIO': 0.1}], proc
+
+
+def waymo_two_stage_data_cfg():
+    """(AUG_CONFIG_LIST, DATA_PROCESSOR) of waymo_models/gd_mae_ts.yaml:18-76: gt_sampling, flip, rotation, scaling,
+    random_world_translation, random_world_drop.  Built by ``input_pipeline.finetune_input_pipeline``."""
+    aug, proc = waymo_finetune_data_cfg()
+    return [aug[0]] + _waymo_late_world_cfg() + [
+        {'NAME': 'random_world_translation', 'PROBABILITY': 0.5, 'NOISE_TRANSLATE_STD': [0.2, 0.2, 0.2]},
+        {'NAME': 'random_world_drop', 'PROBABILITY': 0.5, 'DROP_RATIO': 0.1}], proc
+
+
 class SyntheticDatasetInfo:
     """The attributes ``Detector3DTemplate.build_networks`` reads from the dataset object
     (detector3d_template.py:45-53; dataset.py:27-41; data_processor.py:166-171)."""

@@ -11,6 +11,7 @@ or an explicit permutation for parity tests.  No fallback: without libgdmae_hip.
 """
 from __future__ import annotations
 
+from types import SimpleNamespace
 from typing import List, Optional, Sequence
 
 import numpy as np
@@ -315,18 +316,49 @@ class GpuFinetuneInputPipeline(GpuInputPipeline):
         'num_gt' (host list: kept boxes per frame; 0 is where the reference re-draws another sample), 'sampled_valid'
         (per frame, one flag per candidate)}.  ``params`` / ``candidates`` (per frame [(class name, indices into the
         class's list), ...] in group order) / ``perms``: explicit decisions for parity tests."""
+        return self._run(frames, gt_boxes, gt_names, params, candidates, perms)
+
+    # what GpuFinetuneAugInputPipeline replaces: one frame's draws behind the sampler's, ints behind the packed counts, the launches
+    def _draw_frame_params(self) -> dict:
+        return draw_world_params(self.aug_config) if self.aug_config else {"flip_x": False, "flip_y": False, "angle": 0.0, "scale": 1.0}
+
+    def _extra_meta_ints(self, B: int) -> int:
+        return 0
+
+    def _launch(self, k, ev) -> None:
+        """k: the call's tables and buffers; ev: None or three events (before, between and behind the two launches)."""
+        try:
+            L.call("gdmae_gt_sample_select", k.boxes, k.desc_h.ctypes.data, k.desc, k.group, k.B, k.n_groups, k.tab,
+                   L.host_f32(self.range6), L.host_f32(self.extra_width), self.min_num_corners, k.cap, k.valid, L.ptr(k.rm_boxes),
+                   k.n_valid, k.gt_out, k.num_gt, L.stream())
+        except L.GdmaeHipError as e:
+            if "more than" in str(e):
+                raise NotImplementedError(str(e)) from e
+            raise
+        if ev:
+            ev[1].record()
+        L.call("gdmae_gt_sample_collate", L.ptr(k.raw), L.ptr(k.db), k.F, k.seg, k.S, k.n_rows, k.B, k.tab, k.boxes, k.valid,
+               L.ptr(k.rm_boxes), k.n_valid if self.remove_points else None, L.host_f32(self.xy_range), L.ptr(k.out), k.kept, L.ptr(k.ws),
+               L.stream())
+
+    def _prepare(self, k) -> None:
+        pass
+
+    def _extend_result(self, result: dict, k, extra: list) -> None:
+        pass
+
+    def _run(self, frames, gt_boxes, gt_names, params, candidates, perms, **aug) -> dict:
         B = len(frames)
         F = int(frames[0].shape[1])
         db = self.database
         drawn_c, drawn_p = [], []
-        ident = {"flip_x": False, "flip_y": False, "angle": 0.0, "scale": 1.0}
         for b in range(B):                                  # the reference's order: per frame, the sampler, then the world draws
             if candidates is not None:
                 drawn_c.append(list(candidates[b]))
             else:
                 drawn_c.append(draw_candidates(self.state, gt_names[b]) if self.state is not None else [])
             if params is None:
-                drawn_p.append(draw_world_params(self.aug_config) if self.aug_config else dict(ident))
+                drawn_p.append(self._draw_frame_params())
         params = drawn_p if params is None else params
         if any(len(c) for c in drawn_c) and db is None:
             raise ValueError("candidates without a database")
@@ -367,26 +399,27 @@ class GpuFinetuneInputPipeline(GpuInputPipeline):
         staged_rows = n_scene + (0 if self.resident else n_obj)
         host = self._staging(max(staged_rows, 1) * F).view(-1, F)[:max(staged_rows, 1)]
         hv = host.numpy()
-        seg, row, src, stage = [], 0, 0, n_scene
+        seg, row, src, stage, frame_rows = [], 0, 0, n_scene, [0]
         for b, f in enumerate(frames):
             assert f.dtype == np.float32 and f.shape[1] == F
-            first = 1
+            first, row0 = 1, row                            # column 7: the frame's first virtual row (the drop's row index counts from it)
             for k, e in enumerate(cand_entry[b]):
                 s0, s1 = (int(v) for v in db.offsets[e])
                 if s1 > s0:
                     if self.resident:
-                        seg.append((row, s0, 1, b, desc[b][0] + desc[b][1] + k, desc[b][3] + k, first, 0))
+                        seg.append((row, s0, 1, b, desc[b][0] + desc[b][1] + k, desc[b][3] + k, first, row0))
                     else:
                         hv[stage:stage + s1 - s0] = db.points[s0:s1]
-                        seg.append((row, stage, 0, b, desc[b][0] + desc[b][1] + k, desc[b][3] + k, first, 0))
+                        seg.append((row, stage, 0, b, desc[b][0] + desc[b][1] + k, desc[b][3] + k, first, row0))
                         stage += s1 - s0
                     row += s1 - s0
                     first = 0
             if f.shape[0]:
                 hv[src:src + f.shape[0]] = f
-                seg.append((row, src, 0, b, -1, -1, first, 0))
+                seg.append((row, src, 0, b, -1, -1, first, row0))
                 row += f.shape[0]
                 src += f.shape[0]
+            frame_rows.append(row)
         n_rows, S = row, len(seg)
         assert n_rows < 2 ** 31
         ints_h = np.concatenate([desc_h.reshape(-1), np.asarray(cand_group, np.int32), np.asarray(seg, np.int32).reshape(-1)]).astype(np.int32)
@@ -401,35 +434,29 @@ class GpuFinetuneInputPipeline(GpuInputPipeline):
         flts_d = torch.from_numpy(flts_h).to(dev)
         desc_d, group_d, seg_d = ints_d[:B * 4], ints_d[B * 4:B * 4 + C], ints_d[B * 4 + C:]
         tab_d, boxes_d = flts_d[:B * 8], flts_d[B * 8:]
-        meta = torch.empty(3 * B + 1 + C, dtype=torch.int32, device=dev)      # [kept_off (B + 1) | num_gt (B) | n_valid (B) | valid (C)]
-        kept, num_gt_d, n_valid_d, valid_d = meta[:B + 1], meta[B + 1:2 * B + 1], meta[2 * B + 1:3 * B + 1], meta[3 * B + 1:]
+        n_extra = self._extra_meta_ints(B)
+        meta = torch.empty(3 * B + 1 + C + n_extra, dtype=torch.int32, device=dev)     # [kept_off (B + 1) | num_gt (B) | n_valid (B) | valid (C) | extra]
+        kept, num_gt_d, n_valid_d, valid_d = meta[:B + 1], meta[B + 1:2 * B + 1], meta[2 * B + 1:3 * B + 1], meta[3 * B + 1:3 * B + 1 + C]
         rm_boxes = torch.empty(B, MAX_CANDIDATES, 8, dtype=torch.float32, device=dev)
         gt_out = torch.empty(B, cap, 8, dtype=torch.float32, device=dev)
         out = torch.empty(max(n_rows, 1), 1 + F, dtype=torch.float32, device=dev)
         ws = torch.empty(L.load().gdmae_gt_sample_workspace_bytes(n_rows), dtype=torch.uint8, device=dev)
         dptr = lambda t: t.data_ptr() if t.numel() else None      # noqa: E731  (views of the packed tables; empty ones are never read)
+        k = SimpleNamespace(B=B, F=F, S=S, C=C, n_rows=n_rows, n_groups=n_groups, cap=cap, desc_h=desc_h, frame_rows=frame_rows, dev=dev,
+                            raw=raw, db=db.points_dev if (db is not None and self.resident) else raw, boxes=dptr(boxes_d),
+                            desc=dptr(desc_d), group=dptr(group_d), seg=dptr(seg_d), tab=dptr(tab_d), valid=dptr(valid_d),
+                            n_valid=dptr(n_valid_d), num_gt=dptr(num_gt_d), kept=dptr(kept), gt_out=dptr(gt_out), rm_boxes=rm_boxes, out=out,
+                            ws=ws, extra=meta[3 * B + 1 + C:], params=params, aug=aug)
+        self._prepare(k)
         ev = self.kernel_events = [torch.cuda.Event(enable_timing=True) for _ in range(3)] if self.time_kernels else None
         if ev:
             ev[0].record()
-        try:
-            L.call("gdmae_gt_sample_select", dptr(boxes_d), desc_h.ctypes.data, dptr(desc_d), dptr(group_d), B, n_groups, dptr(tab_d),
-                   L.host_f32(self.range6), L.host_f32(self.extra_width), self.min_num_corners, cap, dptr(valid_d), L.ptr(rm_boxes),
-                   dptr(n_valid_d), dptr(gt_out), dptr(num_gt_d), L.stream())
-        except L.GdmaeHipError as e:
-            if "more than" in str(e):
-                raise NotImplementedError(str(e)) from e
-            raise
-        if ev:
-            ev[1].record()
-        db_d = db.points_dev if (db is not None and self.resident) else raw
-        L.call("gdmae_gt_sample_collate", L.ptr(raw), L.ptr(db_d), F, dptr(seg_d), S, n_rows, B, dptr(tab_d), dptr(boxes_d), dptr(valid_d),
-               L.ptr(rm_boxes), dptr(n_valid_d) if self.remove_points else None, L.host_f32(self.xy_range), L.ptr(out), dptr(kept), L.ptr(ws),
-               L.stream())
+        self._launch(k, ev)
         if ev:
             ev[2].record()
         meta_h = meta.tolist()                              # the one host read of the call: point counts and box counts together
         kept_h, num_gt = meta_h[:B + 1], meta_h[B + 1:2 * B + 1]
-        valid_h = np.asarray(meta_h[3 * B + 1:], dtype=bool)
+        valid_h = np.asarray(meta_h[3 * B + 1:3 * B + 1 + C], dtype=bool)
         n = kept_h[B]
         for b in range(B - 1, -1, -1):
             if kept_h[b] < 0:
@@ -440,5 +467,170 @@ class GpuFinetuneInputPipeline(GpuInputPipeline):
             pts = pts.index_select(0, idx)
         elif self.shuffle and n > 0:
             pts = pts.index_select(0, torch.argsort(pts[:, 0] + torch.rand(n, device=dev)))
-        return {"points": pts, "gt_boxes": gt_out[:, :max(num_gt) if num_gt else 0].contiguous(), "batch_size": B, "num_gt": num_gt,
-                "sampled_valid": [valid_h[d[3]:d[3] + d[2]] for d in desc]}
+        result = {"points": pts, "gt_boxes": gt_out[:, :max(num_gt) if num_gt else 0].contiguous(), "batch_size": B, "num_gt": num_gt,
+                  "sampled_valid": [valid_h[d[3]:d[3] + d[2]] for d in desc]}
+        self._extend_result(result, k, meta_h[3 * B + 1 + C:])
+        return result
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# random_world_translation and random_world_drop ("translation and drop"): the lists of waymo_models/gd_mae_iou.yaml
+# and gd_mae_ts.yaml
+#
+#     gt_sampling -> flip -> rotation -> scaling -> translation -> drop -> heading limit_period -> range masks -> shuffle -> collate
+# ---------------------------------------------------------------------------------------------------------------------
+_WORLD3 = ("random_world_flip", "random_world_rotation", "random_world_scaling")
+_TAIL = ("random_world_translation", "random_world_drop")
+_GOLDEN = 0x9E3779B97F4A7C15
+_M64 = (1 << 64) - 1
+
+
+def drop_keys_of(seed: int, n: int) -> np.ndarray:
+    """The device's 32-bit drop keys of virtual rows 0 .. n - 1 of a frame, restated in numpy uint64: the upper half of splitmix64's
+    finaliser on ``seed + (j + 1) * 0x9E3779B97F4A7C15`` (csrc/gt_sampling.hip: gs_drop_key)."""
+    with np.errstate(over="ignore"):
+        z = np.uint64(int(seed) & _M64) + (np.arange(n, dtype=np.uint64) + np.uint64(1)) * np.uint64(_GOLDEN)
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        return ((z ^ (z >> np.uint64(31))) >> np.uint64(32)).astype(np.uint32)
+
+
+def _enable(p) -> bool:
+    return bool(np.random.choice([False, True], replace=False, p=[1 - p, p]))
+
+
+def draw_translation(cfg) -> np.ndarray:
+    """data_augmentor.py:151-159: the enable draw, then three normals (std 0 when disabled) -> (3) float64."""
+    std = cfg["NOISE_TRANSLATE_STD"] if _enable(cfg["PROBABILITY"]) else [0.0, 0.0, 0.0]
+    if not isinstance(std, list):
+        std = [std, std, std]
+    return np.array([np.random.normal(0, std[0], 1), np.random.normal(0, std[1], 1), np.random.normal(0, std[2], 1)]).T.reshape(3).astype(np.float64)
+
+
+def draw_drop(cfg):
+    """data_augmentor.py:46-47: the enable draw -> q = Python's 1 - DROP_RATIO or 1.0; then the frame's 64-bit seed (the reference draws
+    its k-subset with np.random.choice here: the same distribution, another stream)."""
+    q = 1 - cfg["DROP_RATIO"] if _enable(cfg["PROBABILITY"]) else 1.0
+    hi, lo = (int(v) for v in np.random.randint(0, 1 << 32, 2, dtype=np.uint64))
+    return float(q), (hi << 32) | lo
+
+
+class GpuFinetuneAugInputPipeline(GpuFinetuneInputPipeline):
+    """GpuFinetuneInputPipeline plus ``random_world_translation`` and / or ``random_world_drop`` behind the scaling, in that order.
+    ``params`` dicts may carry ``translate`` (3 float64), ``drop_q`` (1 - DROP_RATIO, or 1.0 for a frame that does not drop) and
+    ``drop_seed``; absent keys mean no translation and no drop.  ``drop_keys``: one uint32 array per frame over its virtual rows (every
+    candidate's object points, then the scene points) instead of the hashed keys.  The result gains ``drop_n`` / ``drop_k`` (host
+    lists: eligible rows and rows the drop keeps, per frame; None when no frame of the batch drops)."""
+
+    def __init__(self, point_cloud_range, class_names, aug_config, database: Optional[GtDatabase] = None, **kw):
+        aug_config = list(aug_config or [])
+        names = [c["NAME"] for c in aug_config]
+        rest = [c for c in aug_config if c["NAME"] not in _TAIL]
+        tail = [c for c in aug_config if c["NAME"] in _TAIL]
+        for n in names:                                     # a foreign name is refused as such, wherever it stands
+            if n not in ("gt_sampling",) + _WORLD3 + _TAIL:
+                raise NotImplementedError(f"augmentation {n} is outside the fine-tune input pipeline")
+        for n in _TAIL:
+            if names.count(n) > 1:
+                raise NotImplementedError(f"augmentation {n} appears twice in the list")
+        bad = next((n for i, n in enumerate(names) if n in _TAIL and any(m not in _TAIL for m in names[i + 1:])), None)     # not at the end
+        if bad is None and [c["NAME"] for c in tail] == list(reversed(_TAIL)):
+            bad = _TAIL[1]                                                                                                   # drop before translation
+        if bad is not None:
+            raise NotImplementedError(f"augmentation {bad} is out of order: the fine-tune input pipeline applies flip, rotation, scaling, "
+                                      "random_world_translation, random_world_drop in this order")
+        super().__init__(point_cloud_range, class_names, rest, database, **kw)
+        self.translate_cfg = next((c for c in tail if c["NAME"] == _TAIL[0]), None)
+        self.drop_cfg = next((c for c in tail if c["NAME"] == _TAIL[1]), None)
+        if self.translate_cfg is not None:
+            std = self.translate_cfg["NOISE_TRANSLATE_STD"]
+            if isinstance(std, (list, tuple)) and len(std) != 3:
+                raise ValueError(f"random_world_translation NOISE_TRANSLATE_STD needs 3 entries or a scalar, got {len(std)}")
+        if self.drop_cfg is not None and not 0.0 <= float(self.drop_cfg["DROP_RATIO"]) <= 1.0:
+            raise ValueError(f"random_world_drop DROP_RATIO {self.drop_cfg['DROP_RATIO']} is outside [0, 1]")
+        self.plan_events = None
+
+    def __call__(self, frames, gt_boxes, gt_names, params=None, candidates=None, perms=None, drop_keys=None) -> dict:
+        return self._run(frames, gt_boxes, gt_names, params, candidates, perms, drop_keys=drop_keys)
+
+    def _draw_frame_params(self) -> dict:
+        p = super()._draw_frame_params()
+        if self.translate_cfg is not None:
+            p["translate"] = draw_translation(self.translate_cfg)
+        if self.drop_cfg is not None:
+            p["drop_q"], p["drop_seed"] = draw_drop(self.drop_cfg)
+        return p
+
+    def _extra_meta_ints(self, B: int) -> int:
+        return 8 * B                                        # the drop plan: [n, k, T, admitted ties, J, ties, 0, 0] per frame
+
+    def _prepare(self, k) -> None:
+        B = k.B
+        t = np.zeros((B, 3), np.float64)
+        q = np.ones(B, np.float64)
+        seeds = np.zeros(B, np.uint64)
+        for b, p in enumerate(k.params):
+            if "translate" in p:
+                if self.translate_cfg is None:
+                    raise ValueError("params carry a translation, but random_world_translation is not in the augmentation list")
+                t[b] = np.asarray(p["translate"], np.float64).reshape(3)
+            if float(p.get("drop_q", 1.0)) != 1.0 and self.drop_cfg is None:
+                raise ValueError("params carry a drop, but random_world_drop is not in the augmentation list")
+            q[b] = float(p.get("drop_q", 1.0))
+            seeds[b] = np.uint64(int(p.get("drop_seed", 0)) & _M64)
+        if ((q < 0) | (q > 1)).any():
+            raise ValueError("drop_q outside [0, 1]")
+        k.plan_on = bool((q != 1.0).any())
+        packed = torch.from_numpy(np.concatenate([t.reshape(-1).view(np.int64), q.view(np.int64), seeds.view(np.int64)])).to(k.dev)
+        k.packed = packed
+        k.translate = packed.data_ptr() if self.translate_cfg is not None else None      # in the list: the add runs, also with t = 0
+        k.q, k.seeds = packed[3 * B:].data_ptr(), packed[4 * B:].data_ptr()
+        k.keys = k.keys_t = k.drop_ws = None
+        if k.plan_on:
+            dk = k.aug.get("drop_keys")
+            if dk is not None and k.n_rows > 0:
+                for b in range(B):
+                    assert len(dk[b]) == k.frame_rows[b + 1] - k.frame_rows[b], "one key per virtual row of the frame"
+                k.keys_t = torch.from_numpy(np.concatenate([np.asarray(a, np.uint32) for a in dk]).view(np.int32)).to(k.dev)
+                k.keys = k.keys_t.data_ptr()
+            k.drop_ws = torch.empty(L.load().gdmae_gt_sample_drop_workspace_bytes(k.n_rows, B), dtype=torch.uint8, device=k.dev)
+
+    def _launch(self, k, ev) -> None:
+        try:
+            L.call("gdmae_gt_sample_select_aug", k.boxes, k.desc_h.ctypes.data, k.desc, k.group, k.B, k.n_groups, k.tab, k.translate,
+                   L.host_f32(self.range6), L.host_f32(self.extra_width), self.min_num_corners, k.cap, k.valid, L.ptr(k.rm_boxes),
+                   k.n_valid, k.gt_out, k.num_gt, L.stream())
+        except L.GdmaeHipError as e:
+            if "more than" in str(e):
+                raise NotImplementedError(str(e)) from e
+            raise
+        if ev:
+            ev[1].record()
+        n_valid = k.n_valid if self.remove_points else None
+        plan = None
+        if k.plan_on:
+            plan = k.extra.data_ptr()
+            pe = self.plan_events = [torch.cuda.Event(enable_timing=True) for _ in range(2)] if ev else None
+            if pe:
+                pe[0].record()
+            L.call("gdmae_gt_sample_drop_plan", L.ptr(k.raw), L.ptr(k.db), k.F, k.seg, k.S, k.n_rows, k.B, k.boxes, k.valid, L.ptr(k.rm_boxes),
+                   n_valid, k.seeds, k.q, k.keys, plan, L.ptr(k.drop_ws), L.stream())
+            if pe:
+                pe[1].record()
+        L.call("gdmae_gt_sample_collate_aug", L.ptr(k.raw), L.ptr(k.db), k.F, k.seg, k.S, k.n_rows, k.B, k.tab, k.translate, k.boxes, k.valid,
+               L.ptr(k.rm_boxes), n_valid, k.seeds, k.keys, plan, L.ptr(k.drop_ws) if plan else None, L.host_f32(self.xy_range), L.ptr(k.out),
+               k.kept, L.ptr(k.ws), L.stream())
+
+    def _extend_result(self, result: dict, k, extra: list) -> None:
+        result["drop_n"] = [extra[8 * b] for b in range(k.B)] if k.plan_on else None
+        result["drop_k"] = [extra[8 * b + 1] for b in range(k.B)] if k.plan_on else None
+
+
+def finetune_input_pipeline(point_cloud_range, class_names, aug_config: Optional[Sequence[dict]] = FINETUNE_AUG_CONFIG,
+                            database: Optional[GtDatabase] = None, **kw) -> GpuFinetuneInputPipeline:
+    """The fine-tune input pipeline of an augmentation list: GpuFinetuneInputPipeline for the list of waymo_models/gd_mae.yaml,
+    GpuFinetuneAugInputPipeline when the list holds ``random_world_translation`` and / or ``random_world_drop`` (gd_mae_iou.yaml,
+    gd_mae_ts.yaml: ``configs.waymo_iou_finetune_data_cfg`` / ``waymo_two_stage_data_cfg``).  Every other name is refused by name."""
+    names = {c["NAME"] for c in (aug_config or [])}
+    cls = GpuFinetuneAugInputPipeline if names & set(_TAIL) else GpuFinetuneInputPipeline
+    return cls(point_cloud_range, class_names, aug_config, database, **kw)

@@ -188,6 +188,10 @@ SIGNATURES = {
     "gdmae_gt_sample_workspace_bytes": (_Z, [_L]),
     "gdmae_gt_sample_select": (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P]),
     "gdmae_gt_sample_collate": (_I, [_P, _P, _I, _P, _I, _L, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "gdmae_gt_sample_drop_workspace_bytes": (_Z, [_L, _I]),
+    "gdmae_gt_sample_select_aug": (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "gdmae_gt_sample_drop_plan": (_I, [_P, _P, _I, _P, _I, _L, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "gdmae_gt_sample_collate_aug": (_I, [_P, _P, _I, _P, _I, _L, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "gdmae_group_workspace_bytes": (_Z, [_L, _L]),
     "gdmae_ingroup_inds": (_I, [_P, _L, _L, _P, _P, _Z, _P]),
     "gdmae_group_inner_inds": (_I, [_P, _L, _L, _I, _P, _P, _Z, _P]),

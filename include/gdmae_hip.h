@@ -842,6 +842,37 @@ int gdmae_gt_sample_collate(const float* raw, const float* db, int F, const int*
                             const int* n_valid, const float* xy_range /* host */, float* out, int* kept_off, void* workspace,
                             void* stream);
 
+/* ---- random_world_translation and random_world_drop in the fine-tune mode ("translation and drop") -- *
+ * Per frame: gt_sampling -> flip -> rotation -> scaling -> translation -> drop -> limit_period -> range masks -> collate.
+ * translate (B, 3) fp64 device or null: every point coordinate and box centre becomes (float)((double)v + t) after the scaling
+ *   (numpy's in-place float32 += float64); the range masks and the corner count see the translated values.  Null: no add.
+ * gdmae_gt_sample_select_aug: gdmae_gt_sample_select with the translation table.
+ * gdmae_gt_sample_drop_plan (called when a frame of the batch drops): a frame's eligible rows are its virtual rows that survive
+ *   gt_sampling (object rows of valid candidates, scene rows in no valid enlarged box); n of them.  k = (long long)(q * (double)n).
+ *   The frame keeps the k eligible rows smallest by (key, virtual row j within the frame).  key = keys[virtual row] when keys is
+ *   given, else the upper 32 bits of splitmix64's finaliser on seeds[frame] + (j + 1) * 0x9E3779B97F4A7C15.
+ *   seg column 7 must hold the first virtual row of the segment's frame.  seeds (B) uint64, q (B) fp64, keys (n_rows) uint32 or
+ *   null: device.  plan (B, 8) int32 device = [n, k, T = key of the k-th row, admitted rows with key T, J = virtual row j of the
+ *   last admitted row with key T (-1: nothing is kept, 0x7fffffff: every tie), rows with key T, 0, 0]: a row is kept when
+ *   key < T || (key == T && j <= J).  drop_ws: gdmae_gt_sample_drop_workspace_bytes(n_rows, B); it also carries every row's
+ *   eligibility to gdmae_gt_sample_collate_aug.  A radix select over (key, j) with integer atomics: deterministic, no host read.
+ * gdmae_gt_sample_collate_aug: gdmae_gt_sample_collate with the translation and, when plan is not null, the scan predicate
+ *   "eligible && kept by the plan && in range (after the translation)"; seeds / keys / plan / drop_ws as the plan call had them. */
+size_t gdmae_gt_sample_drop_workspace_bytes(long long n_rows, int B);
+int gdmae_gt_sample_select_aug(const float* boxes, const int* frame_desc_host, const int* frame_desc, const int* cand_group, int B,
+                               int n_groups, const float* frame_params, const double* translate, const float* range /* host */,
+                               const float* extra_width /* host */, int min_corners, int cap, int* valid, float* rm_boxes,
+                               int* n_valid, float* gt_boxes, int* num_gt, void* stream);
+int gdmae_gt_sample_drop_plan(const float* raw, const float* db, int F, const int* seg, int S, long long n_rows, int B,
+                              const float* boxes, const int* valid, const float* rm_boxes, const int* n_valid,
+                              const unsigned long long* seeds, const double* q, const unsigned* keys, int* plan, void* drop_ws,
+                              void* stream);
+int gdmae_gt_sample_collate_aug(const float* raw, const float* db, int F, const int* seg, int S, long long n_rows, int B,
+                                const float* frame_params, const double* translate, const float* boxes, const int* valid,
+                                const float* rm_boxes, const int* n_valid, const unsigned long long* seeds, const unsigned* keys,
+                                const int* plan, void* drop_ws, const float* xy_range /* host */, float* out, int* kept_off,
+                                void* workspace, void* stream);
+
 /* ---- the reference's own native op API for this path, for arbitrary group ids ------------------- *
  * Drop-in equivalents of pybind module pcdet.ops.sst_ops.sst_ops_cuda (pcdet/ops/sst_ops/src/sst_ops_api.cpp:6-9):
  *   int ingroup_inds_wrapper(at::Tensor group_inds, at::Tensor out_inds)          (sst_ops.cpp:21-33)
